@@ -13,7 +13,15 @@ the boost clock).  Headline mode "fp32" is the diagonal-maximum scorer
 is timed too and reported under "modes".
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode fp32|simd|...] [--frames F]
-                  [--launches L] [--parallel frames|mixtures|densities]
+                  [--launches L] [--parallel frames|mixtures|densities] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and prints
+the line of the headline mode alone.  --dump-outputs DIR writes what the last timed step left in the caller's
+tables (rank 0's): DIR/scores.npy (float32) and, where the mode writes best densities, DIR/best.npy (float64),
+both [mixtures][sampled frames] over a fixed, seeded sample of the step's frames (DUMP_BYTES in all); model and
+frames are seeded, so two builds run with the same arguments can be compared output for output.  --full adds
+everything else described below: the other modes, the CPU baseline, the host boundary, the small-batch and
+drop-in records and, at N > 1, the host leg of all ranks and the fenced density-sharded checks.
 
 --gpus N > 1 without WORLD_SIZE in the environment: this process starts
 `torch.distributed.run --nproc-per-node N bench.py ...` as a child (before any
@@ -32,10 +40,10 @@ the world it joined has N ranks.  Layouts (one process per GPU, RCCL):
 A barrier + synchronize brackets the timed region; the max over ranks is reported.
 
 Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (HIP events
-on its stream, averaged over every launch of the timed region), the CPU baseline
-(oracle restatements of SIMD-diagonal-maximum and diagonal-maximum on this host,
-rank 0 at N=1 only) and the host-buffer boundary rate (gmm_score_host into a
-page-locked table, PCIe included; never `value`).
+on its stream, averaged over every launch of the timed region) and, with --full, the
+CPU baseline (oracle restatements of SIMD-diagonal-maximum and diagonal-maximum on
+this host, rank 0 at N=1 only) and the host-buffer boundary rate (gmm_score_host into
+a page-locked table, PCIe included; never `value`).
 """
 from __future__ import annotations
 
@@ -90,6 +98,10 @@ NN_DIMS = [429] + [2048] * 6 + [5000]
 FENCE_TIMEOUT_S = float(os.environ.get("RASR_BENCH_FENCE_TIMEOUT_S", 150))
 DEADLINE_S = 480.0
 PG_TIMEOUT_S = 180  # the ranks' process group: a collective that hangs aborts the rank instead of outliving the run
+# --dump-outputs: bytes written in all (scores as float32 + best densities as float64 per sampled frame), and the
+# seed of the frame sample
+DUMP_BYTES = 48 << 20
+DUMP_SEED = 20240
 
 
 def parse():
@@ -101,6 +113,13 @@ def parse():
     p.add_argument("--frames", type=int, default=0, help=f"frames per scorer call (default {FRAMES_PER_LAUNCH})")
     p.add_argument("--launches", type=int, default=0, help="scorer calls per step (default: mode-specific)")
     p.add_argument("--parallel", choices=["frames", "mixtures", "densities"], default="frames")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: the other modes, CPU baseline, host boundary, small batches, the "
+                        "drop-in protocol record and (N > 1) the host leg of all ranks and the density-sharded "
+                        "checks, each still subject to its own switch below")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="after the timed steps write the last step's score (and best-density) table, a seeded "
+                        "sample of its frames, as DIR/<name>.npy (rank 0)")
     p.add_argument("--mixtures", type=int, default=5000)
     p.add_argument("--densities", type=int, default=160)
     p.add_argument("--dim", type=int, default=39)
@@ -254,7 +273,25 @@ def _step_slices(total: int, per: int):
     return [(i, min(i + per, total)) for i in range(0, total, per)]
 
 
-def run_mode(args, mode, ms, ws, rank, local, launches):
+def dump_outputs(dump_dir: str, tables: dict) -> None:
+    """--dump-outputs: every table ([rows][frames], on the device) as dump_dir/<name>.npy, float32 (best densities:
+    float64), restricted to one sorted sample of the frame columns drawn with DUMP_SEED -- the same columns for the
+    same table shapes -- so that everything written stays within DUMP_BYTES."""
+    import numpy as np
+    import torch
+    tables = {k: v for k, v in tables.items() if v is not None}
+    rows, cols = next(iter(tables.values())).shape
+    per_col = rows * sum(4 if v.dtype == torch.float32 else 8 for v in tables.values())
+    n = max(1, min(cols, DUMP_BYTES // per_col))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(cols, size=n, replace=False))
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, t in tables.items():
+        sample = t.index_select(1, torch.from_numpy(idx).to(t.device)).cpu().numpy()
+        np.save(os.path.join(dump_dir, f"{name}.npy"),
+                sample if sample.dtype == np.float32 else sample.astype(np.float64))
+
+
+def run_mode(args, mode, ms, ws, rank, local, launches, dump_dir=""):
     import torch
     import rasr_amd as ra
     from rasr_amd import parallel
@@ -282,11 +319,13 @@ def run_mode(args, mode, ms, ws, rank, local, launches):
             if want_best else None)
     stream = torch.cuda.current_stream(dev)
     slices = _step_slices(f_step, fpl)
+    gathered = None  # sharded: what the last launch's score() returned (the assembled table(s))
 
     def step():
+        nonlocal gathered
         for a, b in slices:
             if sharded:  # this rank's mixtures / densities + the collectives, per launch
-                scorer.score(frames[a:b], scores, best, stream)
+                gathered = scorer.score(frames[a:b], scores, best, stream)
             else:
                 sc.score_device(frames[a:b], scores[:, a:b], None if best is None else best[:, a:b], stream)
 
@@ -301,6 +340,14 @@ def run_mode(args, mode, ms, ws, rank, local, launches):
     dt = time.perf_counter() - t0
     kms, nl = sc.kernel_time(reset=True)
     sc.set_timing(False)
+    if dump_dir and rank == 0:
+        if not sharded:
+            dump_outputs(dump_dir, {"scores": scores, "best": best})
+        elif isinstance(gathered, tuple):  # density-sharded: (scores, best densities) of the last launch
+            dump_outputs(dump_dir, {"scores": gathered[0], "best": gathered[1] if want_best else None})
+        elif gathered is not None:  # mixture-sharded: the gathered score table of the last launch
+            dump_outputs(dump_dir, {"scores": gathered})
+    gathered = None
     dt_max = max_over_ranks(dt, ws)
     kms_avg = max_over_ranks(kms / max(nl, 1), ws)
     total_frames = (1 if sharded else ws) * f_step * args.steps
@@ -404,7 +451,7 @@ def run_mode(args, mode, ms, ws, rank, local, launches):
     return res
 
 
-def run_nn(args, ws, rank, local, launches):
+def run_nn(args, ws, rank, local, launches, dump_dir=""):
     """Nn::BatchFeatureScorer drop-in (rasr_amd.nn): one bf16 MFMA GEMM per layer, bias + activation fused;
     a step scores launches x frames on every rank (frame-sharded replicas, no collective)."""
     import numpy as np
@@ -437,6 +484,8 @@ def run_nn(args, ws, rank, local, launches):
     dt = time.perf_counter() - t0
     kms, nl = sc.kernel_time(reset=True)
     sc.set_timing(False)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"scores": scores})
     dt_max = max_over_ranks(dt, ws)
     kms_avg = max_over_ranks(kms / max(nl, 1), ws)
     algo = 2.0 * sum(a * b for a, b in zip(NN_DIMS[:-1], NN_DIMS[1:])) * fpl
@@ -1050,7 +1099,7 @@ def main():
         group = dist.new_group(backend="gloo", timeout=datetime.timedelta(seconds=2 * FENCE_TIMEOUT_S + 120))
     launches = args.launches or DEFAULT_LAUNCHES[args.mode]
     if args.mode == "nn" and not probe:
-        res = run_nn(args, ws, rank, local, launches)
+        res = run_nn(args, ws, rank, local, launches, args.dump_outputs)
         guard.headline_done = True
         if rank == 0:
             guard.line = {
@@ -1077,12 +1126,13 @@ def main():
         counts = (ra.ragged_counts(args.mixtures, args.mixtures * args.densities) if args.ragged else args.densities)
         ms = ra.synthetic_mixture_set(args.mixtures, counts, args.dim, seed=2024,
                                       tying=None if args.tying == "pooled" else args.tying)
-        res = run_mode(args, args.mode, ms, ws, rank, local, launches)
+        res = run_mode(args, args.mode, ms, ws, rank, local, launches, args.dump_outputs)
     guard.headline_done = True
     if rank == 0:
         guard.line = make_line(args, res, ws)
-    multi = ws > 1 and args.parallel == "frames" and args.mode in ("fp32", "simd")
-    if not probe:
+    # everything below is beside the headline: --full only
+    multi = args.full and ws > 1 and args.parallel == "frames" and args.mode in ("fp32", "simd")
+    if not probe and args.full:
         if not args.no_extra_mode:
             # the other headline-model scorers (nn returned above): fp32 / SIMD, and the batched int scorer; the
             # same collectives as the headline

@@ -4,8 +4,8 @@
 # Outputs under gpurun_out/$RUN/ (copy what is to be kept into profiles/).
 #   pytest  : the -m gpu suite (PYTEST_ARGS overrides the selection, e.g. "tests/test_rccl_exchange.py")
 #   smoke   : __graft_entry__.smoke()
-#   bench   : python bench.py (BENCH_ARGS appended)
-#   prof    : rocprofv3 --kernel-trace --stats over bench.py (BENCH_ARGS appended)
+#   bench   : python bench.py --full (BENCH_ARGS appended)
+#   prof    : rocprofv3 --kernel-trace --stats over bench.py --full (BENCH_ARGS appended)
 #   ab-MODE : scripts/ab_bench.py --mode MODE over AB_LIBS (default: the variant libraries), AB_ARGS appended
 #   pmc-MODE: scripts/profile_pmc.sh MODE (one rocprofv3 --pmc pass per counter group, gpurun_out/pmc_MODE)
 #   line-X  : one other bench line, timed alone (X: sum sums d45 d45s pint pfloat nn ragged covm covn covms covsum)
@@ -29,11 +29,11 @@ for s in ${STEPS:-pytest smoke}; do
   case $s in
     pytest) step pytest 1100 python -u -m pytest ${PYTEST_ARGS:-tests -m gpu} -q --timeout 120 --timeout-method thread -p no:cacheprovider ;;
     smoke)  step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)  step bench 900 python bench.py ${BENCH_ARGS} ;;
-    prof)   step prof 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run -- python bench.py ${BENCH_ARGS} ;;
+    bench)  step bench 900 python bench.py --full ${BENCH_ARGS} ;;
+    prof)   step prof 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run -- python bench.py --full ${BENCH_ARGS} ;;
     ab-*)   step "$s" 900 python scripts/ab_bench.py --mode "${s#ab-}" ${AB_ARGS} ${AB_LIBS:-rasr_amd/lib/variants/*.so} ;;
     pmc-*)  step "$s" 1000 bash scripts/profile_pmc.sh "${s#pmc-}" ;;
-    rehearse) RASR_BENCH_SAME_DEVICE=1 RASR_BENCH_BACKEND=gloo step rehearse 420 python bench.py --gpus 2 --steps 3 \
+    rehearse) RASR_BENCH_SAME_DEVICE=1 RASR_BENCH_BACKEND=gloo step rehearse 420 python bench.py --full --gpus 2 --steps 3 \
                 --warmup 1 --no-extra-mode --host-boundary off ;;
     line-*)
       B="--gpus 1 --steps 20 --warmup 3 --cpu-baseline off --host-boundary off --extras off --no-extra-mode"

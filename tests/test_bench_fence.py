@@ -23,7 +23,7 @@ def _run(n, inject=None, deadline=None):
     env.pop("RASR_BENCH_INJECT", None)
     if inject:
         env["RASR_BENCH_INJECT"] = inject
-    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)]
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--full"]  # the checks are --full's
     if deadline:
         args += ["--deadline", str(deadline)]
     t0 = time.monotonic()
