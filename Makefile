@@ -18,13 +18,14 @@ HOSTFLAGS = -O2 -std=c++17 -fPIC -ffp-contract=off -Wall
 
 SRC       = rasr_amd/csrc
 HDRS      = include/rasr_gmm.h $(SRC)/gmm_presel.hh $(SRC)/gmm_prepare.hh $(SRC)/gmm_kernels.hh $(SRC)/gmm_device.hh \
-            $(SRC)/host/GpuFeatureScorer.hh $(SRC)/gmm_hostio.hh include/rasr_gmm_io.h include/rasr_nn.h $(SRC)/nn_kernels.hh $(SRC)/gmm_shard.hh
+            $(SRC)/host/GpuFeatureScorer.hh $(SRC)/gmm_hostio.hh include/rasr_gmm_io.h include/rasr_nn.h $(SRC)/nn_kernels.hh $(SRC)/gmm_shard.hh $(SRC)/gmm_scorer.hh
 
 LIB       = $(LIBDIR)/librasr_gmm.so
 OBJS      = $(BUILD)/gmm_kernels_i8.o $(BUILD)/gmm_kernels_f32.o $(BUILD)/gmm_kernels_split.o $(BUILD)/gmm_api.o $(BUILD)/gmm_prepare.o \
             $(BUILD)/GpuFeatureScorer.o $(BUILD)/MixtureSetFile.o $(BUILD)/MixtureSetEstimatorFile.o $(BUILD)/nn_kernels.o $(BUILD)/nn_api.o \
             $(BUILD)/gmm_kernels_presel.o $(BUILD)/gmm_presel.o $(BUILD)/gmm_kernels_shard.o $(BUILD)/gmm_hostio.o \
-            $(BUILD)/gmm_kernels_direct.o $(BUILD)/gmm_kernels_layout.o $(BUILD)/gmm_shard.o $(BUILD)/gmm_kernels_pairs.o
+            $(BUILD)/gmm_kernels_direct.o $(BUILD)/gmm_kernels_layout.o $(BUILD)/gmm_shard.o $(BUILD)/gmm_kernels_pairs.o \
+            $(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o
 DRIVER    = $(BUILD)/tests/feature_scorer_driver
 
 REFSORT   = $(BUILD)/tests/refsort_test
@@ -98,6 +99,11 @@ $(BUILD)/kernel_id.h: $(KERNEL_OBJS)
 $(BUILD)/gmm_api.o: $(SRC)/gmm_api.cc $(HDRS) $(BUILD)/kernel_id.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HOSTFLAGS) -I$(BUILD) -c $< -o $@
+
+# the other units behind include/rasr_gmm.h (gmm_scorer.hh lists them)
+$(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o: $(BUILD)/%.o: $(SRC)/%.cc $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
 
 $(BUILD)/gmm_hostio.o: $(SRC)/gmm_hostio.cc $(HDRS)
 	@mkdir -p $(BUILD)

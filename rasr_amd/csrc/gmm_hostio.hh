@@ -1,6 +1,6 @@
 // gmm_hostio.hh -- host-buffer side of the boundary (gmm_score_host): a small copy-thread pool and the
 // pinned-memory probe.  The score table of a large batch (n_mixtures x n_frames f32, plus the best
-// densities) is what crosses PCIe; gmm_api.cc streams it back in frame chunks overlapped with the
+// densities) is what crosses PCIe; gmm_hostcall.cc streams it back in frame chunks overlapped with the
 // scoring of the next chunk, straight into the caller's buffer when that buffer is pinned, otherwise
 // through a double-buffered pinned staging ring whose host-side copies run on this pool.
 #pragma once

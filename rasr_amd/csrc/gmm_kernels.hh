@@ -6,9 +6,27 @@
 #include <cstdint>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <utility>
 
 namespace rasr_gmm {
+
+// the scorer kernels.  The host picks one per handle (gmm_score.cc kernelPlanOf; planFor adds a call's frame tile)
+// and lays the frame tables, the grid and the chunk tables out for it.  The split launcher is told the kernel.  The
+// quantized launcher is deliberately left as it was: it reads the same choice from I8Args (presel, scoreOnly,
+// smallTile), which the host fills from the plan and the kernels themselves read.
+enum class Kernel { I8Seg, I8Cls, I8Presel, Direct, SplitPair, SplitWide, SplitPresel, Split32, SplitSum, Split32Sum, F32 };
+constexpr bool isSplitKernel(Kernel k) {
+    return k == Kernel::SplitPair || k == Kernel::SplitWide || k == Kernel::SplitPresel || k == Kernel::Split32 ||
+           k == Kernel::SplitSum || k == Kernel::Split32Sum;
+}
+
+// f(std::integral_constant<int, N>) for the N of the list that equals v; false if none does (no such instantiation).
+// The launchers list N largest first: the kernels are emitted in the reverse of that order, as before
+template <int... N, class F>
+bool dispatchInt(uint32_t v, std::integer_sequence<int, N...>, F&& f) {
+    return ((v == uint32_t(N) ? (f(std::integral_constant<int, N>{}), true) : false) || ...);
+}
 
 // hipFuncAttributeMaxDynamicSharedMemorySize for `fn` on the current device, once per (kernel, device): a
 // process may drive several GPUs (gmm_scorer_create_sharded, one handle per GPU), and the attribute belongs to
@@ -184,8 +202,8 @@ hipError_t launchPrepareFramesSplit(const float* frames, uint32_t nFrames, uint3
 hipError_t launchPrepareFramesSplitCov(const float* frames, uint32_t nFrames, uint32_t frameStride, uint32_t nFramesRead,
                                        uint32_t D, uint32_t kSteps, const float* centre, const float* dimScale,
                                        const int32_t* limbExp, void* frameH, int32_t* frameExp, hipStream_t stream);
-hipError_t launchScoreSplit(const SplitArgs& a, uint32_t rows, uint32_t kSteps, hipStream_t stream);
-hipError_t launchScoreSplitSum(const SplitArgs& a, uint32_t rows, uint32_t kSteps, hipStream_t stream);  // diagonal-sum
+// kernel: one of Kernel::Split*; hipErrorInvalidValue where it has no instantiation at kSteps
+hipError_t launchScoreSplit(const SplitArgs& a, Kernel kernel, uint32_t kSteps, hipStream_t stream);
 constexpr uint32_t kSplit32MaxKSteps = 10;  // 32-row split kernel instantiated for K/16 <= 10 (D <= 51)
 hipError_t launchScoreI8(const I8Args& a, uint32_t kSteps, bool multiCov, hipStream_t stream);
 

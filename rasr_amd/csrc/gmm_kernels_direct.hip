@@ -30,7 +30,7 @@ __device__ __forceinline__ const __attribute__((address_space(4))) T* cst(const 
     return (const __attribute__((address_space(4))) T*)p;
 }
 
-// Row layout (host, gmm_api.cc prepareDirect), L = 4 NB + 4 floats per mean / isv row and per frame:
+// Row layout (host, gmm_prepare.cc prepareDirect), L = 4 NB + 4 floats per mean / isv row and per frame:
 // diagonal-maximum: dims 0 .. 4 nfb - 1 in the first 4 nfb slots (zeros up to 4 NB), the D % 4 remaining
 // dims in the last 4 slots (zeros after them); batch-float: dims 0 .. D - 1, zeros up to 4 NB.  Zero slots
 // add exactly +0 to a non-negative sum, so every density runs the same branch-free code.
@@ -190,18 +190,10 @@ hipError_t launchScoreDirect(const DirectArgs& a, hipStream_t stream) {
     if (nb == 0 || a.Dp != 4u * nb + 4u)  // the host laid the rows out for exactly this instantiation
         return hipErrorInvalidValue;
     const bool multi = a.multiCov != 0;
-    switch (nb) {
-        case 2: launchDirectNB<2>(a, multi, grid, stream); break;
-        case 4: launchDirectNB<4>(a, multi, grid, stream); break;
-        case 6: launchDirectNB<6>(a, multi, grid, stream); break;
-        case 8: launchDirectNB<8>(a, multi, grid, stream); break;
-        case 10: launchDirectNB<10>(a, multi, grid, stream); break;
-        case 12: launchDirectNB<12>(a, multi, grid, stream); break;
-        case 16: launchDirectNB<16>(a, multi, grid, stream); break;
-        case 24: launchDirectNB<24>(a, multi, grid, stream); break;
-        default: launchDirectNB<32>(a, multi, grid, stream); break;
-    }
-    return hipGetLastError();
+    // the block counts directBlocks returns
+    const bool ok = dispatchInt(nb, std::integer_sequence<int, 32, 24, 16, 12, 10, 8, 6, 4, 2>{},
+                                [&](auto n) { launchDirectNB<decltype(n)::value>(a, multi, grid, stream); });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace rasr_gmm

@@ -270,32 +270,18 @@ hipError_t launchPrepareFramesF32(const float* frames, uint32_t nFrames, uint32_
 
 template <int KS>
 static void launchF32K(const F32Args& a, bool multi, uint32_t grid, hipStream_t s) {
-    if (multi)
-        hipLaunchKernelGGL((dev::scoreF32<kF32NF, KS, true>), dim3(grid), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((dev::scoreF32<kF32NF, KS, false>), dim3(grid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((multi ? dev::scoreF32<kF32NF, KS, true> : dev::scoreF32<kF32NF, KS, false>), dim3(grid), dim3(256),
+                       0, s, a);
 }
 
 hipError_t launchScoreF32(const F32Args& a, uint32_t kSteps, bool multiCov, hipStream_t stream) {
     const uint32_t grid = 8u * ((a.nChunks + 7u) / 8u) * a.nFrameTiles;
     if (grid == 0)
         return hipSuccess;
-    switch (kSteps) {
-        case 2: launchF32K<2>(a, multiCov, grid, stream); break;
-        case 4: launchF32K<4>(a, multiCov, grid, stream); break;
-        case 6: launchF32K<6>(a, multiCov, grid, stream); break;
-        case 8: launchF32K<8>(a, multiCov, grid, stream); break;
-        case 10: launchF32K<10>(a, multiCov, grid, stream); break;
-        case 12: launchF32K<12>(a, multiCov, grid, stream); break;
-        case 14: launchF32K<14>(a, multiCov, grid, stream); break;
-        case 16: launchF32K<16>(a, multiCov, grid, stream); break;
-        case 20: launchF32K<20>(a, multiCov, grid, stream); break;
-        case 24: launchF32K<24>(a, multiCov, grid, stream); break;
-        case 28: launchF32K<28>(a, multiCov, grid, stream); break;
-        case 32: launchF32K<32>(a, multiCov, grid, stream); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    // the K steps of f32KStepsInstantiated (gmm_prepare.hh)
+    const bool ok = dispatchInt(kSteps, std::integer_sequence<int, 32, 28, 24, 20, 16, 14, 12, 10, 8, 6, 4, 2>{},
+                                [&](auto ks) { launchF32K<decltype(ks)::value>(a, multiCov, grid, stream); });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace rasr_gmm

@@ -1611,14 +1611,9 @@ hipError_t launchPrepareFramesSplit(const float* frames, uint32_t nFrames, uint3
                                     const float* dimScale,
                                     const int32_t* limbExp, void* frameH, float* frameXX, int32_t* frameExp,
                                     hipStream_t stream) {
-    if (rows == 32)
-        hipLaunchKernelGGL(dev::prepareFramesSplit<32>, dim3((nFramesRead + 7) / 8), dim3(256), 0, stream, frames,
-                           nFrames, frameStride, nFramesRead, D, kSteps, isv, centre, dimScale, limbExp,
-                           static_cast<dev::u32x4*>(frameH), frameXX, frameExp);
-    else
-        hipLaunchKernelGGL(dev::prepareFramesSplit<16>, dim3((nFramesRead + 7) / 8), dim3(256), 0, stream, frames,
-                           nFrames, frameStride, nFramesRead, D, kSteps, isv, centre, dimScale, limbExp,
-                           static_cast<dev::u32x4*>(frameH), frameXX, frameExp);
+    hipLaunchKernelGGL((rows == 32 ? dev::prepareFramesSplit<32> : dev::prepareFramesSplit<16>), dim3((nFramesRead + 7) / 8),
+                       dim3(256), 0, stream, frames, nFrames, frameStride, nFramesRead, D, kSteps, isv, centre, dimScale,
+                       limbExp, static_cast<dev::u32x4*>(frameH), frameXX, frameExp);
     return hipGetLastError();
 }
 
@@ -1631,18 +1626,17 @@ hipError_t launchPrepareFramesSplitCov(const float* frames, uint32_t nFrames, ui
     return hipGetLastError();
 }
 
+// kernel: the host's choice (gmm_score.cc planFor); every branch below is instantiated for every KS
 template <int KS>
-static void launchSplitK(const SplitArgs& a, uint32_t grid, hipStream_t s) {
+static void launchSplitK(const SplitArgs& a, Kernel kernel, uint32_t grid, hipStream_t s) {
     if constexpr (splitWideFrames(KS) != 0) {
-        if (!a.presel) {
-            if (a.best)
-                hipLaunchKernelGGL((dev::scoreSplitWide<KS, true>), dim3(grid), dim3(64), 0, s, a, a.mixTileOff);
-            else
-                hipLaunchKernelGGL((dev::scoreSplitWide<KS, false>), dim3(grid), dim3(64), 0, s, a, a.mixTileOff);
+        if (kernel == Kernel::SplitWide) {
+            hipLaunchKernelGGL((a.best ? dev::scoreSplitWide<KS, true> : dev::scoreSplitWide<KS, false>), dim3(grid), dim3(64),
+                               0, s, a, a.mixTileOff);
             return;
         }
     }
-    if (a.presel) {  // preselection-batch-float: no best density; the waves' mask tables in dynamic LDS
+    if (kernel == Kernel::SplitPresel) {  // preselection-batch-float: no best density; the waves' mask tables in dynamic LDS
         // the block's 256 frames = 4 tables of [clusters][16] words, whatever the waves
         const uint32_t lds = kSplitFramesPerBlock / 64u * a.nClusters * 64u;
         (void)allowDynamicLds(reinterpret_cast<const void*>(&dev::scoreSplit<KS, false, true>),
@@ -1650,112 +1644,61 @@ static void launchSplitK(const SplitArgs& a, uint32_t grid, hipStream_t s) {
         hipLaunchKernelGGL((dev::scoreSplit<KS, false, true>), dim3(grid), dim3(kSplitFramesPerBlock / splitPreselNF(KS) * 4),
                            lds, s, a, a.mixTileOff);
     }
-    else if (a.best)
-        hipLaunchKernelGGL((dev::scoreSplit<KS, true, false>), dim3(grid), dim3(64 * kSplitMainWaves), 0, s, a,
-                           a.mixTileOff);
     else
-        hipLaunchKernelGGL((dev::scoreSplit<KS, false, false>), dim3(grid), dim3(64 * kSplitMainWaves), 0, s, a,
-                           a.mixTileOff);
+        hipLaunchKernelGGL((a.best ? dev::scoreSplit<KS, true, false> : dev::scoreSplit<KS, false, false>), dim3(grid),
+                           dim3(64 * kSplitMainWaves), 0, s, a, a.mixTileOff);
 }
 
+// with or without best densities: the BEST instantiation of the kernel (both have the same signature)
 template <int KS>
 static void launchSplit32K(const SplitArgs& a, uint32_t grid, hipStream_t s) {
-    if (a.best)
-        hipLaunchKernelGGL((dev::scoreSplit32<KS, true>), dim3(grid), dim3(64 * (kSplitFramesPerBlock / (32 * GMM_SPLIT32_NB))),
-                           0, s, a, a.mixTileOff);
-    else
-        hipLaunchKernelGGL((dev::scoreSplit32<KS, false>), dim3(grid), dim3(64 * (kSplitFramesPerBlock / (32 * GMM_SPLIT32_NB))),
-                           0, s, a, a.mixTileOff);
-}
-
-hipError_t launchScoreSplit(const SplitArgs& a, uint32_t rows, uint32_t kSteps16, hipStream_t stream) {
-    const uint32_t grid = 8u * ((a.nChunks + 7u) / 8u) * a.nFrameTiles;
-    if (grid == 0)
-        return hipSuccess;
-    if (a.presel && (rows != 16 || a.nClusters == 0 || a.nClusters > 256 || !a.selT || !a.tileClu))
-        return hipErrorInvalidValue;  // the mask tables are laid out for 16-row tiles and <= 256 clusters
-    if (rows == 32) {
-        switch (kSteps16) {
-            case 1: launchSplit32K<1>(a, grid, stream); break;
-            case 2: launchSplit32K<2>(a, grid, stream); break;
-            case 3: launchSplit32K<3>(a, grid, stream); break;
-            case 4: launchSplit32K<4>(a, grid, stream); break;
-            case 5: launchSplit32K<5>(a, grid, stream); break;
-            case 6: launchSplit32K<6>(a, grid, stream); break;
-            case 7: launchSplit32K<7>(a, grid, stream); break;
-            case 8: launchSplit32K<8>(a, grid, stream); break;
-            case 9: launchSplit32K<9>(a, grid, stream); break;
-            case 10: launchSplit32K<10>(a, grid, stream); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (kSteps16) {
-        case 1: launchSplitK<1>(a, grid, stream); break;
-        case 2: launchSplitK<2>(a, grid, stream); break;
-        case 3: launchSplitK<3>(a, grid, stream); break;
-        case 4: launchSplitK<4>(a, grid, stream); break;
-        case 5: launchSplitK<5>(a, grid, stream); break;
-        case 6: launchSplitK<6>(a, grid, stream); break;
-        case 7: launchSplitK<7>(a, grid, stream); break;
-        case 8: launchSplitK<8>(a, grid, stream); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    hipLaunchKernelGGL((a.best ? dev::scoreSplit32<KS, true> : dev::scoreSplit32<KS, false>), dim3(grid),
+                       dim3(64 * (kSplitFramesPerBlock / (32 * GMM_SPLIT32_NB))), 0, s, a, a.mixTileOff);
 }
 
 template <int KS>
 static void launchSplitSumK(const SplitArgs& a, uint32_t grid, hipStream_t s) {
-    if (a.best)
-        hipLaunchKernelGGL((dev::scoreSplitSum<KS, true>), dim3(grid), dim3(kSplitFramesPerBlock / GMM_SPLIT_SUM_NF * 4), 0,
-                           s, a, a.mixTileOff);
-    else
-        hipLaunchKernelGGL((dev::scoreSplitSum<KS, false>), dim3(grid), dim3(kSplitFramesPerBlock / GMM_SPLIT_SUM_NF * 4),
-                           0, s, a, a.mixTileOff);
+    hipLaunchKernelGGL((a.best ? dev::scoreSplitSum<KS, true> : dev::scoreSplitSum<KS, false>), dim3(grid),
+                       dim3(kSplitFramesPerBlock / GMM_SPLIT_SUM_NF * 4), 0, s, a, a.mixTileOff);
 }
 
 template <int KS>
 static void launchSplit32SumK(const SplitArgs& a, uint32_t grid, hipStream_t s) {
-    if (a.best)
-        hipLaunchKernelGGL((dev::scoreSplit32Sum<KS, true>), dim3(grid), dim3(64 * (kSplitFramesPerBlock / 128)), 0, s, a,
-                           a.mixTileOff);
-    else
-        hipLaunchKernelGGL((dev::scoreSplit32Sum<KS, false>), dim3(grid), dim3(64 * (kSplitFramesPerBlock / 128)), 0, s,
-                           a, a.mixTileOff);
+    hipLaunchKernelGGL((a.best ? dev::scoreSplit32Sum<KS, true> : dev::scoreSplit32Sum<KS, false>), dim3(grid),
+                       dim3(64 * (kSplitFramesPerBlock / 128)), 0, s, a, a.mixTileOff);
 }
 
-hipError_t launchScoreSplitSum(const SplitArgs& a, uint32_t rows, uint32_t kSteps16, hipStream_t stream) {
+// the K steps the 16-row and the 32-row kernels are instantiated for (kSplit32MaxKSteps)
+using KSteps16 = std::integer_sequence<int, 8, 7, 6, 5, 4, 3, 2, 1>;
+using KSteps32 = std::integer_sequence<int, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1>;
+
+hipError_t launchScoreSplit(const SplitArgs& a, Kernel kernel, uint32_t kSteps16, hipStream_t stream) {
     const uint32_t grid = 8u * ((a.nChunks + 7u) / 8u) * a.nFrameTiles;
     if (grid == 0)
         return hipSuccess;
-    if (rows == 32) {
-        switch (kSteps16) {
-            case 1: launchSplit32SumK<1>(a, grid, stream); break;
-            case 2: launchSplit32SumK<2>(a, grid, stream); break;
-            case 3: launchSplit32SumK<3>(a, grid, stream); break;
-            case 4: launchSplit32SumK<4>(a, grid, stream); break;
-            case 5: launchSplit32SumK<5>(a, grid, stream); break;
-            case 6: launchSplit32SumK<6>(a, grid, stream); break;
-            case 7: launchSplit32SumK<7>(a, grid, stream); break;
-            case 8: launchSplit32SumK<8>(a, grid, stream); break;
-            case 9: launchSplit32SumK<9>(a, grid, stream); break;
-            case 10: launchSplit32SumK<10>(a, grid, stream); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
+    if ((a.presel != 0) != (kernel == Kernel::SplitPresel) ||
+        (a.presel && (a.nClusters == 0 || a.nClusters > 256 || !a.selT || !a.tileClu)) ||
+        (kernel == Kernel::SplitWide && splitWideFrames(kSteps16) == 0))
+        return hipErrorInvalidValue;  // the mask tables are laid out for 16-row tiles and <= 256 clusters; no wide kernel
+    bool ok = false;
+    switch (kernel) {
+        case Kernel::Split32:
+            ok = dispatchInt(kSteps16, KSteps32{}, [&](auto ks) { launchSplit32K<decltype(ks)::value>(a, grid, stream); });
+            break;
+        case Kernel::SplitPair:
+        case Kernel::SplitWide:
+        case Kernel::SplitPresel:
+            ok = dispatchInt(kSteps16, KSteps16{}, [&](auto ks) { launchSplitK<decltype(ks)::value>(a, kernel, grid, stream); });
+            break;
+        case Kernel::Split32Sum:
+            ok = dispatchInt(kSteps16, KSteps32{}, [&](auto ks) { launchSplit32SumK<decltype(ks)::value>(a, grid, stream); });
+            break;
+        case Kernel::SplitSum:
+            ok = dispatchInt(kSteps16, KSteps16{}, [&](auto ks) { launchSplitSumK<decltype(ks)::value>(a, grid, stream); });
+            break;
+        default: break;
     }
-    switch (kSteps16) {
-        case 1: launchSplitSumK<1>(a, grid, stream); break;
-        case 2: launchSplitSumK<2>(a, grid, stream); break;
-        case 3: launchSplitSumK<3>(a, grid, stream); break;
-        case 4: launchSplitSumK<4>(a, grid, stream); break;
-        case 5: launchSplitSumK<5>(a, grid, stream); break;
-        case 6: launchSplitSumK<6>(a, grid, stream); break;
-        case 7: launchSplitSumK<7>(a, grid, stream); break;
-        case 8: launchSplitSumK<8>(a, grid, stream); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace rasr_gmm

@@ -354,7 +354,7 @@ int nn_score_host_ex(nn_scorer* s, const float* frames, uint32_t nFrames, uint32
     // table are written (the rest stays untouched, as with gmm_score_host)
     // small calls (<= 64 frames) with page-locked buffers the device addresses at the same pointer: no copy engine,
     // a kernel gathers the frame rows and the transpose / a strided copy kernel writes the caller's table over PCIe
-    // (as gmm_score_host_ring's small calls, gmm_api.cc scoreHostSmall)
+    // (as gmm_score_host_ring's small calls, gmm_hostcall.cc scoreHostSmall)
     static const bool smallOn = [] {  // RASR_GMM_SMALL_HOST=0: the copy-engine path (A/B)
         const char* e = std::getenv("RASR_GMM_SMALL_HOST");
         return !(e && e[0] == '0');

@@ -1,6 +1,6 @@
 """The RCCL exchange of the density-sharded layout, executed on one GPU.
 
-gmm_scorer_create_sharded's RCCL exchange (gmm_api.cc groupScore) folds the keys of the parts that share a GPU
+gmm_scorer_create_sharded's RCCL exchange (gmm_group.cc groupScore) folds the keys of the parts that share a GPU
 into that GPU's first part (minIntoShardKeys) and then all-reduces (ncclMin, ncclInt64, in place) over one rank
 per distinct GPU.  With every part on device 0 this is a ONE-rank communicator (ncclCommInitAll over [0]) and the
 very ncclGroupStart / ncclAllReduce / ncclGroupEnd sequence an 8-GPU handle issues -- the path a one-GPU box can

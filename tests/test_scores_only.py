@@ -1,7 +1,7 @@
 """Calls without best densities (the search's score(e)): the score-only paths.
 
 * SIMD-diagonal-maximum keeps a second copy of its model on the score-only class layout (the `scoresOnly` twin,
-  gmm_api.cc; gmm_prepare.cc buildClassLayout): a call with best_density NULL runs scoreI8Seg<SCORE_ONLY> with
+  gmm_create.cc; gmm_prepare.cc buildClassLayout): a call with best_density NULL runs scoreI8Seg<SCORE_ONLY> with
   the SIMD constants and finalize.  Its scores must be BIT-EXACT against the oracle (SimdFeatureScorer.cc:135-176)
   and against the key layout, on ragged, tiny and empty mixtures, shards, score scales, strided device frames and
   the quantizer's edge frames.  Models the class layout cannot hold (D > 64, several covariances) keep the key
