@@ -65,9 +65,6 @@ constexpr int splitPreselNF(int ks) { return GMM_SPLIT_PRESEL_NF == 8 && ks <= 5
 #ifndef GMM_SPLIT_TAG_EMIT
 #define GMM_SPLIT_TAG_EMIT 0  // 1: a tile's keys carry (tile << 2) only; the slot r is OR-ed in at the mixture's end
 #endif
-#ifndef GMM_SPLIT_EMIT_FLAT
-#define GMM_SPLIT_EMIT_FLAT 1  // the emit finalize without the exec-mask branch (A/B at 128 frames per wave: -0.25..-0.5 %)
-#endif
 
 namespace rasr_gmm {
 namespace dev {
@@ -281,88 +278,152 @@ __global__ __launch_bounds__(256) void prepareFramesSplitCov(const float* __rest
 // as the u32 bits of the float with the low keyBits mantissa bits replaced by (tile << 2 | r), r the
 // accumulator slot (row 4g + r of the tile in lane group g).  Positive floats order like their bits,
 // so one v_and_or_b32 per value and one v_min3_u32 per two values keep, per lane and slot, the
-// minimum by (value, tile); the lane group g is resolved at the end of the mixture, where keys
-// equal in value and tag prefer the lower group (lower density index).
+// minimum by (value, tile, r); the lane group g is resolved at the end of the mixture, where keys
+// equal in value and tag prefer the lower group (of rows 4g + r with one r, the lower density index).
 // ---------------------------------------------------------------------------
-// end of a mixture: the 4 slot keys of each column block -> (score, density) per frame, reduced
-// across the four 16-lane groups by permlane swaps (r0 of a swap always comes from the lower group);
-// lane l stores frame frame0 + l.  Straight-line code (no branch splits the basic block it is
-// scheduled into): uniform options are arithmetic, the frame bound is the buffer's num_records.
+// end of a mixture: the slot keys of each column block -> (score, density) per frame.  Straight-line code
+// without a select: the cross-lane reduce is permlane swap + v_min_u32 (reduceKeysSplit), uniform options are
+// arithmetic, the frame bound is the buffer's num_records, and the cases the arithmetic forms get wrong (no
+// finite candidate, batch-float's overflowed total) are mended behind ONE uniform branch per emit that ordinary
+// frames never take (finalizeSplit).
 // ---------------------------------------------------------------------------
-template <bool BEST>
-__device__ __forceinline__ void emitKeysSplit(const SplitArgs& a, const uint32_t (&k)[4], uint32_t m, uint32_t frame0,
-                                              int lane, uint32_t g, uint32_t kmask, int eOut, float noneScore);
+__device__ __forceinline__ uint32_t usubSat(uint32_t x, uint32_t y) {
+    return __builtin_elementwise_sub_sat(x, y);  // v_sub_u32 clamp: x - y where x > y, else 0
+}
 
+// 1 in an SGPR the compiler cannot see through: min(x, 1) stays one v_min_u32 (a visible 1 turns it, and the
+// bitwise mux it feeds, back into v_cmp + v_cndmask_b32)
+__device__ __forceinline__ uint32_t opaqueOne() {
+    uint32_t one = 1u;
+    asm("" : "+s"(one));
+    return one;
+}
+
+// the per-block minima k[cb] (over the block's slots; lane group g of a lane holds rows 4g .. 4g+3 of every tile)
+// -> in lane l the minimum key of block l >> 4, column l & 15, and (BEST) the lane group it came from.
+// The key alone decides: r0 of a swap always comes from the lower group, so v_min_u32 keeps it on a tie, and the
+// saturated difference r0 - r1 is non-zero exactly where the upper group's key is smaller.  Adjacent groups first,
+// {0, 1} and {2, 3}, then the two pairs against each other: at both stages every group on the r0 side is below
+// every group on the r1 side, so of equal keys the lowest group (the lowest density index) wins.  (The
+// compare-and-select reduce this replaces paired {g, g + 2} first and returned group 2 where groups 1 and 2, or
+// 1, 2 and 3, held the minimum and group 0 did not.)
+// The two opaque values (opaqueOne, all) keep the compiler from folding the forms back into v_cmp + v_cndmask_b32;
+// the instruction counts in DESIGN.md section 9 were read from ROCm 7.2.0's compiler.
 template <bool BEST>
-__device__ __forceinline__ void emitMixtureSplit(const SplitArgs& a, const uint32_t (&best)[4][4], uint32_t m,
-                                                 uint32_t frame0, int lane, uint32_t g, uint32_t kmask, int eOut,
+__device__ __forceinline__ void reduceKeysSplit(const uint32_t (&k)[4], uint32_t& key, uint32_t& grp) {
+    // even lane groups keep blocks 0, 2, odd ones blocks 1, 3
+    uint32_t w[2], d[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const auto r = __builtin_amdgcn_permlane16_swap(k[2 * p], k[2 * p + 1], false, false);
+        w[p]         = min(r[0], r[1]);
+        d[p]         = usubSat(r[0], r[1]);
+    }
+    // lanes < 32 keep blocks 0, 1, lanes >= 32 blocks 2, 3: lane l ends with block l >> 4
+    const auto rk = __builtin_amdgcn_permlane32_swap(w[0], w[1], false, false);
+    key           = min(rk[0], rk[1]);
+    grp           = 0;
+    if constexpr (BEST) {
+        const auto     rd  = __builtin_amdgcn_permlane32_swap(d[0], d[1], false, false);
+        const uint32_t one = opaqueOne();
+        const uint32_t hi  = min(usubSat(rk[0], rk[1]), one);  // 1: the minimum came from groups {2, 3}
+        uint32_t       all = 0u - hi;
+        asm("" : "+v"(all));  // opaque: the mux below stays bitwise (v_and + v_and_or), no v_cndmask_b32
+        const uint32_t lo = min((rd[1] & all) | (rd[0] & ~all), one);  // the winning pair's difference: odd group
+        grp               = (hi << 1) | lo;
+    }
+}
+
+// keys of NH 64-frame halves (and, BEST, the densities idx the keys' tags and groups give) -> scores; idx becomes
+// 0xffffffff where the mixture has no finite candidate.  SELECT (preselection, where a mixture without a selected
+// density is an everyday case): the exact rule for every lane, no branch.
+template <bool BEST, int NH, bool SELECT = false>
+__device__ __forceinline__ void finalizeSplit(const SplitArgs& a, const uint32_t (&key)[NH], uint32_t kmask,
+                                              const int (&eOut)[NH], float noneScore, float (&score)[NH],
+                                              uint32_t (&idx)[NH]) {
+    constexpr uint32_t kNoneBits = __builtin_bit_cast(uint32_t, 1e37f);
+    constexpr int32_t  kOverBits = __builtin_bit_cast(int32_t, 3.40282347e+38f);
+    float    kv[NH], total[NH];
+    uint32_t kvMax  = 0;
+    int32_t  totMax = 0;
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        // midpoint of the masked bits: within 2^-(24 - keyBits) of the minimum's value
+        const uint32_t kb = (key[h] & ~kmask) | ((kmask + 1u) >> 1);
+        kv[h]             = __uint_as_float(kb);
+        total[h]          = __fsub_rn(ldexpf(kv[h], eOut[h]), a.offsetK0);
+        score[h]          = __fmul_rn(a.outScale, 0.5f * total[h]);  // diagonal-maximum: 0.5 total
+        kvMax             = max(kvMax, kb);
+        totMax            = max(totMax, __builtin_bit_cast(int32_t, total[h]));
+    }
+    // a superset of the lanes the forms above get wrong, as two integer tests on the maxima over the halves: key
+    // bits of 1e37 and above (infinities, NaNs and the all-ones key of either sign) and totals of FLT_MAX and above
+    // (a NaN total comes from a NaN key).  The rare path is the exact float rule.
+    if (SELECT || __builtin_expect(__builtin_amdgcn_ballot_w64(kvMax >= kNoneBits || totMax >= kOverBits) != 0, 0)) {
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            const bool none = !(kv[h] < 1e37f);  // no finite candidate (empty mixture, non-finite frame)
+            // batch-float keeps an overflowed total (BatchFeatureScorer.cc:468)
+            const bool over = a.flavor == 3 && !(total[h] < 3.40282347e+38f);
+            score[h]        = none ? noneScore : __fmul_rn(a.outScale, over ? total[h] : 0.5f * total[h]);
+            if constexpr (BEST)
+                idx[h] = none ? 0xffffffffu : idx[h];
+        }
+    }
+}
+
+// buffer resources of mixture m's score and best-density rows; frames >= nFrames fall outside num_records: the
+// buffer store drops them (a multi-dword store per dword)
+#define GMM_SPLIT_ROW_RSRC(a, ptr, m)                                                                               \
+    __builtin_amdgcn_make_buffer_rsrc((ptr) + static_cast<size_t>((m) - (a).mixBase) * (a).scoreStride, (short)0, \
+                                      static_cast<int>((a).nFrames * 4u), 0x00020000)
+
+// scoreSplit: best[4 h + cb][slot] of NH halves; lane l stores frames frame0 + 64 h + l
+template <bool BEST, int NH, bool SELECT>
+__device__ __forceinline__ void emitMixtureSplit(const SplitArgs& a, const uint32_t (&best)[4 * NH][4], uint32_t m,
+                                                 uint32_t frame0, int lane, uint32_t kmask, const int (&eOut)[NH],
                                                  float noneScore) {
 #if GMM_SPLIT_DIAG_NOEMIT  // diagnostic (wrong results): the emit's cost, the minima kept live by one XOR chain
     {
         uint32_t x = 0;
 #pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
+        for (int cb = 0; cb < 4 * NH; ++cb)
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 x ^= best[cb][r];
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc(a.scores + static_cast<size_t>(m - a.mixBase) * a.scoreStride,
-                                                         (short)0, static_cast<int>(a.nFrames * 4u), 0x00020000);
-        __builtin_amdgcn_raw_buffer_store_b32(x, rs, static_cast<uint32_t>(frame0 + lane) * 4u, 0, GMM_STORE_CPOL);
+        __builtin_amdgcn_raw_buffer_store_b32(x, GMM_SPLIT_ROW_RSRC(a, a.scores, m),
+                                              static_cast<uint32_t>(frame0 + lane) * 4u, 0, GMM_STORE_CPOL);
         return;
     }
 #endif
-    uint32_t k[4];
+    uint32_t key[NH], idx[NH];
+    float    score[NH];
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-        if (GMM_SPLIT_TAG_EMIT && kmask)  // slot r's keys carry tile << 2 only: r joins here (all ones stay)
-            k[cb] = min(umin3(best[cb][0], best[cb][1] | 1u, best[cb][2] | 2u), best[cb][3] | 3u);
-        else
-            k[cb] = min(umin3(best[cb][0], best[cb][1], best[cb][2]), best[cb][3]);
-    }
-    emitKeysSplit<BEST>(a, k, m, frame0, lane, g, kmask, eOut, noneScore);
-}
-
-// the per-block minima k[cb] (over the block's slots, lane group g of the tile rows in every lane) -> (score,
-// density) of frame frame0 + lane
-template <bool BEST>
-__device__ __forceinline__ void emitKeysSplit(const SplitArgs& a, const uint32_t (&k)[4], uint32_t m, uint32_t frame0,
-                                              int lane, uint32_t g, uint32_t kmask, int eOut, float noneScore) {
-    // groups {g&1, g&1|2} of blocks (0,2) and (1,3): lanes < 32 keep blocks 0, 1, lanes >= 32 blocks 2, 3
-    uint32_t w[2], wg[2];
+    for (int h = 0; h < NH; ++h) {
+        uint32_t k[4], grp;
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const auto r    = __builtin_amdgcn_permlane32_swap(k[p], k[p + 2], false, false);
-        const bool take = r[1] < r[0];
-        w[p]            = take ? r[1] : r[0];
-        wg[p]           = (g & 1u) | (take ? 2u : 0u);
+        for (int cb = 0; cb < 4; ++cb) {
+            const uint32_t(&b)[4] = best[4 * h + cb];
+            if (GMM_SPLIT_TAG_EMIT && kmask)  // slot r's keys carry tile << 2 only: r joins here (all ones stay)
+                k[cb] = min(umin3(b[0], b[1] | 1u, b[2] | 2u), b[3] | 3u);
+            else
+                k[cb] = min(umin3(b[0], b[1], b[2]), b[3]);
+        }
+        reduceKeysSplit<BEST>(k, key[h], grp);
+        idx[h] = (((key[h] & kmask & ~3u) | grp) << 2) | (key[h] & 3u);  // tile << 4 | group << 2 | slot
     }
-    // groups {even, odd} rows: lane l keeps block l >> 4
-    const auto     rk   = __builtin_amdgcn_permlane16_swap(w[0], w[1], false, false);
-    const auto     rg   = __builtin_amdgcn_permlane16_swap(wg[0], wg[1], false, false);
-    const bool     take = rk[1] < rk[0];
-    const uint32_t key  = take ? rk[1] : rk[0];
-    const uint32_t grp  = take ? rg[1] : rg[0];
-
-    // midpoint of the masked bits: within 2^-(24 - keyBits) of the minimum's value
-    const float kv    = __uint_as_float((key & ~kmask) | ((kmask + 1u) >> 1));
-    const bool  none  = !(kv < 1e37f);  // no finite candidate (empty mixture, non-finite frame)
-    float       total = __fsub_rn(ldexpf(kv, eOut), a.offsetK0);
-    if (GMM_SPLIT_EMIT_FLAT)
-        asm volatile("" : "+v"(total));  // computed for every lane: the select below stays a v_cndmask
-    // diagonal-maximum: 0.5 total; batch-float keeps an overflowed total (BatchFeatureScorer.cc:468)
-    const float score = none ? noneScore
-                             : __fmul_rn(a.outScale, (a.flavor == 3 && !(total < 3.40282347e+38f)) ? total : 0.5f * total);
-    const uint32_t idx = none ? 0xffffffffu : ((((key & kmask) >> 2) << 4) | (grp << 2) | (key & 3u));
-    const uint32_t mo  = m - a.mixBase;
-    const uint32_t off = static_cast<uint32_t>(frame0 + lane) * 4u;
-    // frames >= nFrames fall outside num_records: the buffer store drops them
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(a.scores + static_cast<size_t>(mo) * a.scoreStride, (short)0,
-                                                     static_cast<int>(a.nFrames * 4u), 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(score), rs, off, 0, GMM_STORE_CPOL);
+    finalizeSplit<BEST, NH, SELECT>(a, key, kmask, eOut, noneScore, score, idx);
+    const auto rs = GMM_SPLIT_ROW_RSRC(a, a.scores, m);
+#pragma unroll
+    for (int h = 0; h < NH; ++h)
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(score[h]), rs,
+                                              static_cast<uint32_t>(frame0 + 64u * h + lane) * 4u, 0, GMM_STORE_CPOL);
     if constexpr (BEST) {
-        const auto rb = __builtin_amdgcn_make_buffer_rsrc(a.best + static_cast<size_t>(mo) * a.scoreStride, (short)0,
-                                                         static_cast<int>(a.nFrames * 4u), 0x00020000);
-        __builtin_amdgcn_raw_buffer_store_b32(idx, rb, off, 0, GMM_STORE_CPOL);
+        const auto rb = GMM_SPLIT_ROW_RSRC(a, a.best, m);
+#pragma unroll
+        for (int h = 0; h < NH; ++h)
+            __builtin_amdgcn_raw_buffer_store_b32(idx[h], rb, static_cast<uint32_t>(frame0 + 64u * h + lane) * 4u, 0,
+                                                  GMM_STORE_CPOL);
     }
 }
 
@@ -547,10 +608,7 @@ __global__ __launch_bounds__(PRESEL ? kSplitFramesPerBlock / splitPreselNF(KS) *
     uint32_t m = m0, tBeg = T0, tEnd = m0 < m1 ? mixTileOff[m0 + 1] : T0;
     resetBest();
     const auto emit = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int h = 0; h < NH; ++h)
-            emitMixtureSplit<BEST>(a, *reinterpret_cast<const uint32_t(*)[4][4]>(&best[4 * h]), m, frame0 + 64u * h,
-                                   lane, g, kmask, eOut[h], noneScore);
+        emitMixtureSplit<BEST, NH, PRESEL>(a, best, m, frame0, lane, kmask, eOut, noneScore);
     };
     // after an emit at tile tNext: next mixture, and the empty ones that also end there (rare path)
     const auto advance = [&](uint32_t tNext) __attribute__((always_inline)) {
@@ -683,17 +741,24 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
         for (int s = 0; s < KS; ++s)
             A[s] = th[(static_cast<size_t>(tt) * KS + s) * 64 + lane];
     };
-    const f16x8* fh = static_cast<const f16x8*>(a.frameH);
-    f16x8        B[NF][KS];
+    // Frames of the column blocks: column c of block 4 h + q is frame frame0 + NH (16 q + c) + h, so that the
+    // emit's reduce, which leaves block 4 h + q of half h in lane 16 q + c, ends with the NH consecutive frames
+    // frame0 + NH lane + h in every lane: one multi-dword store per output row.  The frame fragments lie
+    // [frame / 16][step][16 k-group + frame % 16] (prepareFramesSplit): a gather, once per workgroup.
+    const f16x8*   fh = static_cast<const f16x8*>(a.frameH);
+    const uint32_t kq = g * 16u, c = static_cast<uint32_t>(lane) & 15u;
+    f16x8          B[NF][KS];
 #pragma unroll
-    for (int cb = 0; cb < NF; ++cb)
+    for (int cb = 0; cb < NF; ++cb) {
+        const uint32_t fl = NH * (16u * (cb % 4) + c) + cb / 4;  // the column's frame in the wave
 #pragma unroll
         for (int s = 0; s < KS; ++s)
-            B[cb][s] = fh[(static_cast<size_t>(fb0 + cb) * KS + s) * 64 + lane];
+            B[cb][s] = fh[(static_cast<size_t>(fb0 + fl / 16u) * KS + s) * 64 + kq + fl % 16u];
+    }
     int eOut[NH];
 #pragma unroll
     for (int h = 0; h < NH; ++h)
-        eOut[h] = a.frameExp[frame0 + 64u * h + lane];
+        eOut[h] = a.frameExp[frame0 + NH * lane + h];
     // the frame operands complete before the tile prefetch, then pinned to the accumulator file
 #pragma unroll
     for (int cb = 0; cb < NF; ++cb)
@@ -755,13 +820,37 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
 
     uint32_t   m = m0, tBeg = T0, tEnd = m0 < m1 ? mixTileOff[m0 + 1] : T0;
     const auto emit = [&]() __attribute__((always_inline)) {
+        uint32_t key[NH], idx[NH];
+        float    score[NH];
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
-            uint32_t k[4];
+            uint32_t k[4], grp;
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb)
                 k[cb] = min(best[4 * h + cb][0], best[4 * h + cb][1]);
-            emitKeysSplit<BEST>(a, k, m, frame0 + 64u * h, lane, g, kmask, eOut[h], noneScore);
+            reduceKeysSplit<BEST>(k, key[h], grp);
+            idx[h] = (((key[h] & kmask & ~3u) | grp) << 2) | (key[h] & 3u);  // tile << 4 | group << 2 | slot
+        }
+        finalizeSplit<BEST, NH>(a, key, kmask, eOut, noneScore, score, idx);
+        // lane l holds frames frame0 + NH l + h: one store per row (4 halves: buffer_store_dwordx4)
+        const uint32_t off = (frame0 + NH * static_cast<uint32_t>(lane)) * 4u;
+        const auto     rs  = GMM_SPLIT_ROW_RSRC(a, a.scores, m);
+        if constexpr (NH == 4)
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(score[0]), __float_as_uint(score[1]),
+                                                         __float_as_uint(score[2]), __float_as_uint(score[3])},
+                                                   rs, off, 0, GMM_STORE_CPOL);
+        else
+#pragma unroll
+            for (int h = 0; h < NH; ++h)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(score[h]), rs, off + 4u * h, 0, GMM_STORE_CPOL);
+        if constexpr (BEST) {
+            const auto rb = GMM_SPLIT_ROW_RSRC(a, a.best, m);
+            if constexpr (NH == 4)
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{idx[0], idx[1], idx[2], idx[3]}, rb, off, 0, GMM_STORE_CPOL);
+            else
+#pragma unroll
+                for (int h = 0; h < NH; ++h)
+                    __builtin_amdgcn_raw_buffer_store_b32(idx[h], rb, off + 4u * h, 0, GMM_STORE_CPOL);
         }
     };
     const auto advance = [&](uint32_t tNext) __attribute__((always_inline)) {
@@ -841,39 +930,50 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
 // the epilogue of the previous tile.  Keys: value bits with the low keyBits replaced by
 // (tile << 4 | i); four slots per block keep the minimum over registers {q, q+4, q+8, q+12}.
 // ---------------------------------------------------------------------------
-template <bool BEST>
-__device__ __forceinline__ void emitMixtureSplit32(const SplitArgs& a, const uint32_t (&best)[2][4], uint32_t m,
-                                                   uint32_t frame0, int lane, uint32_t kmask, int eOut,
+// The emit of NH 64-frame halves (best[2 h + b][slot]; lane l stores frames frame0 + 64 h + l) is select-free as
+// the 16-row kernels' (reduceKeysSplit, finalizeSplit).
+template <bool BEST, int NH>
+__device__ __forceinline__ void emitMixtureSplit32(const SplitArgs& a, const uint32_t (&best)[2 * NH][4], uint32_t m,
+                                                   uint32_t frame0, int lane, uint32_t kmask, const int (&eOut)[NH],
                                                    float noneScore) {
-    uint32_t k[2];
+    uint32_t key[NH], idx[NH];
+    float    score[NH];
 #pragma unroll
-    for (int b = 0; b < 2; ++b)
-        k[b] = min(umin3(best[b][0], best[b][1], best[b][2]), best[b][3]);
-    // lanes < 32 keep block 0, lanes >= 32 block 1; r[0] from lane half h = 0, r[1] from h = 1
-    const auto     r    = __builtin_amdgcn_permlane32_swap(k[0], k[1], false, false);
-    // (value, tile) first, then the row in the tile: row(i, h) = (i & 3) + 8 (i >> 2) + 4 h
-    const uint32_t hi0  = r[0] & ~15u, hi1 = r[1] & ~15u;
-    const uint32_t row0 = (r[0] & 3u) | ((r[0] & 12u) << 1), row1 = ((r[1] & 3u) | ((r[1] & 12u) << 1)) + 4u;
-    // scores only: untagged values, the plain minimum
-    const bool     take = BEST ? (hi1 < hi0 || (hi1 == hi0 && row1 < row0)) : r[1] < r[0];
-    const uint32_t key  = take ? r[1] : r[0];
-    const uint32_t row  = take ? row1 : row0;
-
-    const float kv    = __uint_as_float((key & ~kmask) | ((kmask + 1u) >> 1));
-    const bool  none  = !(kv < 1e37f);
-    const float total = __fsub_rn(ldexpf(kv, eOut), a.offsetK0);
-    const float score = none ? noneScore
-                             : __fmul_rn(a.outScale, (a.flavor == 3 && !(total < 3.40282347e+38f)) ? total : 0.5f * total);
-    const uint32_t idx = none ? 0xffffffffu : ((((key & kmask) >> 4) << 5) | row);
-    const uint32_t mo  = m - a.mixBase;
-    const uint32_t off = static_cast<uint32_t>(frame0 + lane) * 4u;
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(a.scores + static_cast<size_t>(mo) * a.scoreStride, (short)0,
-                                                     static_cast<int>(a.nFrames * 4u), 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(score), rs, off, 0, GMM_STORE_CPOL);
+    for (int h = 0; h < NH; ++h) {
+        uint32_t k[2];
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+            k[b] = min(umin3(best[2 * h + b][0], best[2 * h + b][1], best[2 * h + b][2]), best[2 * h + b][3]);
+        // lanes < 32 keep block 0, lanes >= 32 block 1; r[0] from lane half 0, r[1] from lane half 1
+        const auto r = __builtin_amdgcn_permlane32_swap(k[0], k[1], false, false);
+        if constexpr (BEST) {
+            // (value, tile) first, then the row in the tile, row(i, half) = (i & 3) + 8 (i >> 2) + 4 half: half 1
+            // wins exactly where its key without the low two bits of i is smaller (an equal i >> 2 is half 0's, the
+            // lower row), which the saturated difference tells without a compare
+            const uint32_t up  = min(usubSat(r[0] >> 2, r[1] >> 2), opaqueOne());
+            uint32_t       all = 0u - up;
+            asm("" : "+v"(all));  // opaque: the mux stays bitwise
+            key[h] = (r[1] & all) | (r[0] & ~all);
+            const uint32_t row = (key[h] & 3u) | ((key[h] & 12u) << 1) | (up << 2);
+            idx[h]             = (((key[h] & kmask) >> 4) << 5) | row;
+        }
+        else {  // scores only: untagged values, the plain minimum
+            key[h] = min(r[0], r[1]);
+            idx[h] = 0;
+        }
+    }
+    finalizeSplit<BEST, NH>(a, key, kmask, eOut, noneScore, score, idx);
+    const auto rs = GMM_SPLIT_ROW_RSRC(a, a.scores, m);
+#pragma unroll
+    for (int h = 0; h < NH; ++h)
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(score[h]), rs,
+                                              static_cast<uint32_t>(frame0 + 64u * h + lane) * 4u, 0, GMM_STORE_CPOL);
     if constexpr (BEST) {
-        const auto rb = __builtin_amdgcn_make_buffer_rsrc(a.best + static_cast<size_t>(mo) * a.scoreStride, (short)0,
-                                                         static_cast<int>(a.nFrames * 4u), 0x00020000);
-        __builtin_amdgcn_raw_buffer_store_b32(idx, rb, off, 0, GMM_STORE_CPOL);
+        const auto rb = GMM_SPLIT_ROW_RSRC(a, a.best, m);
+#pragma unroll
+        for (int h = 0; h < NH; ++h)
+            __builtin_amdgcn_raw_buffer_store_b32(idx[h], rb, static_cast<uint32_t>(frame0 + 64u * h + lane) * 4u, 0,
+                                                  GMM_STORE_CPOL);
     }
 }
 
@@ -984,10 +1084,7 @@ __global__ __launch_bounds__(64 * (kSplitFramesPerBlock / (32 * GMM_SPLIT32_NB))
     uint32_t m = m0, tBeg = T0, tEnd = m0 < m1 ? mixTileOff[m0 + 1] : T0;
     resetBest();
     const auto emit = [&]() {
-#pragma unroll
-        for (int h = 0; h < NH; ++h)
-            emitMixtureSplit32<BEST>(a, *reinterpret_cast<const uint32_t(*)[2][4]>(&best[2 * h]), m, frame0 + 64u * h,
-                                     lane, kmask, eOut[h], noneScore);
+        emitMixtureSplit32<BEST, NH>(a, best, m, frame0, lane, kmask, eOut, noneScore);
     };
     const auto advance = [&](uint32_t tNext) {
         ++m;
