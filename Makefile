@@ -25,13 +25,17 @@ OBJS      = $(BUILD)/gmm_kernels_i8.o $(BUILD)/gmm_kernels_f32.o $(BUILD)/gmm_ke
             $(BUILD)/GpuFeatureScorer.o $(BUILD)/MixtureSetFile.o $(BUILD)/MixtureSetEstimatorFile.o $(BUILD)/nn_kernels.o $(BUILD)/nn_api.o \
             $(BUILD)/gmm_kernels_presel.o $(BUILD)/gmm_presel.o $(BUILD)/gmm_kernels_shard.o $(BUILD)/gmm_hostio.o \
             $(BUILD)/gmm_kernels_direct.o $(BUILD)/gmm_kernels_layout.o $(BUILD)/gmm_shard.o $(BUILD)/gmm_kernels_pairs.o \
-            $(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o
+            $(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o \
+            $(BUILD)/gmm_kernels_accum.o $(BUILD)/gmm_estimator.o
+# include/rasr_gmm_estimator.h: the units behind it depend on these besides HDRS
+EST_HDRS  = include/rasr_gmm_estimator.h $(SRC)/gmm_estimator.hh
 DRIVER    = $(BUILD)/tests/feature_scorer_driver
 
 REFSORT   = $(BUILD)/tests/refsort_test
 CLASSLAYOUT = $(BUILD)/tests/class_layout_test
+ESTCOMBINE = $(BUILD)/tests/estimator_combine_test
 
-all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) oracle check-integration
+all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) oracle check-integration
 
 $(BUILD)/gmm_kernels_i8.o: $(SRC)/gmm_kernels_i8.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -60,6 +64,16 @@ $(BUILD)/gmm_kernels_direct.o: $(SRC)/gmm_kernels_direct.hip $(HDRS)
 $(BUILD)/gmm_kernels_pairs.o: $(SRC)/gmm_kernels_pairs.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
+
+# maximum-likelihood accumulation (gmm_estimator_accumulate_*): resolve, inverted indexes (rocPRIM radix sort),
+# ordered f64 sums.  Not one of KERNEL_OBJS: gmm_kernel_id names the scoring kernels the PMC summaries measure
+$(BUILD)/gmm_kernels_accum.o: $(SRC)/gmm_kernels_accum.hip $(EST_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/gmm_estimator.o: $(SRC)/gmm_estimator.cc $(HDRS) $(EST_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
 
 # density-sharded exchange keys (BASELINE config 4)
 $(BUILD)/gmm_kernels_shard.o: $(SRC)/gmm_kernels_shard.hip $(HDRS)
@@ -126,7 +140,7 @@ $(BUILD)/MixtureSetFile.o: $(SRC)/host/MixtureSetFile.cc $(HDRS)
 	@mkdir -p $(BUILD)
 	g++ $(HOSTFLAGS) -c $< -o $@
 
-$(BUILD)/MixtureSetEstimatorFile.o: $(SRC)/host/MixtureSetEstimatorFile.cc $(HDRS)
+$(BUILD)/MixtureSetEstimatorFile.o: $(SRC)/host/MixtureSetEstimatorFile.cc $(HDRS) $(EST_HDRS)
 	@mkdir -p $(BUILD)
 	g++ $(HOSTFLAGS) -c $< -o $@
 
@@ -144,6 +158,12 @@ $(CLASSLAYOUT): tests/cpp/class_layout_test.cc $(BUILD)/gmm_prepare.o $(HDRS)
 $(REFSORT): tests/cpp/refsort_test.cc $(SRC)/gmm_refsort.hh
 	@mkdir -p $(BUILD)/tests
 	g++ -std=c++17 -O2 -Wall -o $@ $<
+
+# host check of gmm_estimator_combine and the estimator file writer (no GPU, no HIP): the two file units alone
+$(ESTCOMBINE): tests/cpp/estimator_combine_test.cc $(SRC)/host/MixtureSetEstimatorFile.cc $(SRC)/host/MixtureSetFile.cc \
+               $(HDRS) $(EST_HDRS)
+	@mkdir -p $(BUILD)/tests
+	g++ $(HOSTFLAGS) $(ESTCOMBINE_FLAGS) -o $@ $< $(SRC)/host/MixtureSetEstimatorFile.cc $(SRC)/host/MixtureSetFile.cc -lz
 
 $(DRIVER): tests/cpp/feature_scorer_driver.cc $(LIB) $(HDRS)
 	@mkdir -p $(BUILD)/tests

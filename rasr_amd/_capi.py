@@ -14,6 +14,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RASR_GMM_LIB") or os.path.join(_HERE, "lib", "librasr_gmm.so")
 
 GMM_OK = 0
+GMM_ERR_INVALID_ARGUMENT = -1
+GMM_ERR_UNSUPPORTED = -2
+GMM_ERR_DEVICE = -3
+GMM_ERR_OUT_OF_MEMORY = -4
+GMM_ERR_CAPACITY = -5
+GMM_ESTIMATOR_CHUNK = 512  # include/rasr_gmm_estimator.h: part of the accumulation's numeric contract
 GMM_FLAG_NATIVE_F32 = 1  # gmm_scorer_config.flags
 GMM_FLAG_SPLIT_TILE16 = 2
 GMM_FLAG_SPLIT_TILE32 = 4
@@ -100,7 +106,7 @@ GMM_HOST_ASYNC = 8
 # gmm_scorer_create_sharded: the per-frame reduce of mixtures split between GPUs
 GMM_EXCHANGE = {"auto": 0, "rccl": 1, "copy": 2}
 
-# (name, restype, argtypes) for every function declared in include/rasr_gmm.h and rasr_gmm_io.h
+# (name, restype, argtypes) for every function declared in include/rasr_gmm.h, rasr_gmm_io.h and rasr_gmm_estimator.h
 PROTOTYPES = [
     ("gmm_default_config", None, [ctypes.POINTER(ScorerConfig)]),
     ("gmm_scorer_create", ctypes.c_int,
@@ -173,6 +179,28 @@ PROTOTYPES = [
      [ctypes.c_char_p, ctypes.POINTER(EstimatorConfig), ctypes.c_uint32, ctypes.c_uint32,
       ctypes.POINTER(MixtureSetDesc)]),
     ("gmm_mixture_set_write", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(MixtureSetDesc), ctypes.c_uint32]),
+    # include/rasr_gmm_estimator.h
+    ("gmm_estimator_create", ctypes.c_int,
+     [ctypes.POINTER(MixtureSetDesc), ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    ("gmm_estimator_destroy", ctypes.c_int, [ctypes.c_void_p]),
+    ("gmm_estimator_reset", ctypes.c_int, [ctypes.c_void_p]),
+    ("gmm_estimator_accumulate_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("gmm_estimator_accumulate_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    ("gmm_estimator_skipped", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("gmm_estimator_get", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("gmm_estimator_serialize", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    ("gmm_estimator_write", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    ("gmm_estimator_estimate", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(EstimatorConfig), ctypes.POINTER(MixtureSetDesc)]),
+    ("gmm_estimator_combine", ctypes.c_int,
+     [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     ("gmm_version", ctypes.c_char_p, []),
     ("gmm_kernel_id", ctypes.c_char_p, []),
 ]
@@ -210,10 +238,12 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
 
 
 class GmmError(RuntimeError):
-    pass
+    code = None  # the status the call returned (GMM_ERR_*)
 
 
 def check(rc: int, what: str = "") -> None:
     if rc != GMM_OK:
         msg = load_library().gmm_last_error()
-        raise GmmError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+        err = GmmError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+        err.code = rc
+        raise err

@@ -161,7 +161,8 @@ int setupPairs(gmm_scorer* s, const gmm_mixture_set& ms, ShardRange shard, const
         return GMM_OK;
     if ((rc = upload(t->dMixOff, mixOff)) || (rc = upload(t->dCov, cov)))
         return rc;
-    s->pairs = std::move(t);
+    t->nEntries = ee - eb;
+    s->pairs    = std::move(t);
     return GMM_OK;
 }
 

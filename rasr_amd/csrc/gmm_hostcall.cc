@@ -415,7 +415,9 @@ int gmm_fetch_best_density(gmm_scorer* s, uint64_t callId, uint32_t* best, uint3
     return rc;
 }
 
-namespace {
+}  // extern "C"
+
+namespace rasr_gmm {
 PairArgs pairArgsOf(const gmm_scorer* s, const float* frames, uint32_t nFrames, uint32_t frameStride) {
     PairArgs a{};
     a.frames      = frames;
@@ -448,7 +450,9 @@ int checkPairs(const gmm_scorer* s) {
                                          "float model of dimension > 128): use gmm_fetch_best_density");
     return GMM_OK;
 }
-}  // namespace
+}  // namespace rasr_gmm
+
+extern "C" {
 
 int gmm_best_density_pairs(gmm_scorer* s, uint64_t callId, const uint32_t* positions, const uint32_t* mixtures,
                            uint32_t nPairs, uint32_t* best) {

@@ -184,6 +184,7 @@ struct Preselection {
 struct PairTables {
     int                    kind = kPairSimd;
     uint32_t               L = 0, nb = 0, isvStride = 0;
+    uint32_t               nEntries = 0;  // mixture entries of the shard (rows of the tables below)
     DeviceBuffer<uint32_t> dMixOff, dCov;
     DeviceBuffer<uint8_t>  dQMean;
     DeviceBuffer<int32_t>  dQConst;
@@ -303,6 +304,10 @@ int        scoreImpl(gmm_scorer* s, const float* frames, uint32_t nFrames, uint3
 // the GMM_HOST_ASYNC call in flight, if any, is complete on return: its staging (frames, prepared frames,
 // device tables) is free for the next call of any kind
 int waitAsync(gmm_scorer* s);
+
+// gmm_hostcall.cc: the sparse best-density path (also the Viterbi branch of gmm_estimator_accumulate_*)
+int      checkPairs(const gmm_scorer* s);  // GMM_ERR_UNSUPPORTED: batch types, sharded handles, no pair tables
+PairArgs pairArgsOf(const gmm_scorer* s, const float* frames, uint32_t nFrames, uint32_t frameStride);
 
 // gmm_group.cc
 int groupScore(gmm_scorer* s, const float* frames, uint32_t nFrames, uint32_t frameStride, float* scores,

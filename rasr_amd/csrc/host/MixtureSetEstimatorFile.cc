@@ -14,6 +14,11 @@
 //   Mixture::addDensity / normalizeWeights     src/Mm/Mixture.cc:63-74, logExpNorm Utilities.hh:44-51
 // Core::BinaryInputStream: native (little-endian) byte order, no compression.
 //
+// The other direction (include/rasr_gmm_estimator.h): writeEstimatorFile is the writer of such a file,
+//   AbstractMixtureSetEstimator::write         src/Mm/AbstractMixtureSetEstimator.cc:416-420, 481-509
+// and gmm_estimator_combine the trainer's combine action over several of them,
+//   accumulate(Core::BinaryInputStreams&, os)  src/Mm/AbstractMixtureSetEstimator.cc:171-290.
+//
 // The arithmetic follows the reference in f64 with the reference's operation order, results stored as
 // f32 means / variances and f64 log weights.  One order is not defined by the reference: the covariance
 // estimate sums the squared mean statistics of the covariance's means in the iteration order of an
@@ -31,6 +36,7 @@
 #include <vector>
 
 #include "../../../include/rasr_gmm_io.h"
+#include "../gmm_estimator.hh"
 
 namespace rasr_gmm {
 void setLastError(const std::string& msg);
@@ -126,7 +132,123 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
+struct Writer {  // Core::BinaryOutputStream into a byte vector
+    std::vector<unsigned char> bytes;
+    template <class T>
+    void put(T v) {
+        const unsigned char* p = reinterpret_cast<const unsigned char*>(&v);
+        bytes.insert(bytes.end(), p, p + sizeof(T));
+    }
+    void header(uint32_t dimension) {  // writeHeader (cc:416-420) and the dimension (cc:485)
+        const char magic[8] = {'M', 'I', 'X', 'S', 'E', 'T', 0, 0};
+        bytes.insert(bytes.end(), magic, magic + 8);
+        put<uint32_t>(2);  // version_
+        put<uint32_t>(dimension);
+    }
+    void accumulator(const double* sum, size_t n, double weight) {  // VectorAccumulator::write
+        put<uint32_t>(static_cast<uint32_t>(n));
+        for (size_t k = 0; k < n; ++k)
+            put<double>(sum[k]);
+        put<double>(weight);
+    }
+};
+
+// one estimator file as gmm_estimator_combine reads it
+struct EstimatorFile {
+    uint32_t                 version = 0, dimension = 0;
+    std::vector<Accumulator> means, covs;
+    std::vector<DensityEst>  dens;
+    std::vector<MixtureEst>  mix;
+};
+
+// "" or what is wrong with the file
+std::string readEstimatorFile(const void* data, uint64_t size, EstimatorFile& f) {
+    static const unsigned char empty = 0;
+    const unsigned char* b = data ? static_cast<const unsigned char*>(data) : &empty;
+    Reader r{b, b + (data ? size : 0)};
+    char magic[8];
+    for (char& c : magic)
+        c = static_cast<char>(r.get<uint8_t>());
+    if (r.fail || std::memcmp(magic, "MIXSET", 7) != 0)
+        return "magic \"MIXSET\" expected";
+    f.version   = r.get<uint32_t>();
+    f.dimension = r.get<uint32_t>();
+    for (std::vector<Accumulator>* accs : {&f.means, &f.covs}) {
+        const uint32_t n = r.get<uint32_t>();
+        for (uint32_t i = 0; i < n && !r.fail; ++i) {
+            accs->emplace_back();
+            accs->back().read(r, f.version);
+        }
+    }
+    const uint32_t nDens = r.get<uint32_t>();
+    for (uint32_t i = 0; i < nDens && !r.fail; ++i) {
+        DensityEst d;
+        d.mean = r.get<uint32_t>();
+        d.cov  = r.get<uint32_t>();
+        f.dens.push_back(d);
+    }
+    const uint32_t nMix = r.get<uint32_t>();
+    for (uint32_t m = 0; m < nMix && !r.fail; ++m) {
+        MixtureEst     x;
+        const uint32_t n = r.get<uint32_t>();
+        if (r.fail || static_cast<uint64_t>(n) * 8 > static_cast<uint64_t>(r.end - r.p)) {
+            r.fail = true;
+            break;
+        }
+        for (uint32_t j = 0; j < n && !r.fail; ++j) {
+            x.dens.push_back(r.get<uint32_t>());
+            x.weights.push_back(f.version > 0 ? r.get<double>() : static_cast<double>(r.get<uint32_t>()));
+        }
+        f.mix.push_back(std::move(x));
+    }
+    if (r.fail)
+        return "truncated file";
+    for (const std::vector<Accumulator>* accs : {&f.means, &f.covs})
+        for (const Accumulator& a : *accs)
+            if (a.sum.size() != f.dimension)
+                return "an accumulator's size differs from the dimension";
+    return "";
+}
+
 }  // namespace
+
+namespace rasr_gmm {
+
+std::vector<unsigned char> writeEstimatorFile(const EstimatorTables& t) {
+    // MixtureSetEstimatorIndexMap (cc:804-817): first appearance over the mixtures, then their densities
+    IndexMap meanMap(t.nMeans), covMap(t.nCovs), densMap(t.nDens);
+    for (uint32_t e = 0; e < t.mixOff[t.nMix]; ++e) {
+        const uint32_t d = t.mixDens[e];
+        meanMap.add(t.dnsMean[d]);
+        covMap.add(t.dnsCov[d]);
+        densMap.add(d);
+    }
+    const size_t D = t.D;
+    Writer       w;
+    w.header(t.D);
+    w.put<uint32_t>(static_cast<uint32_t>(meanMap.order.size()));
+    for (uint32_t m : meanMap.order)
+        w.accumulator(t.meanSums + m * D, D, t.meanWeights[m]);
+    w.put<uint32_t>(static_cast<uint32_t>(covMap.order.size()));
+    for (uint32_t c : covMap.order)
+        w.accumulator(t.covSums + c * D, D, t.covWeights[c]);
+    w.put<uint32_t>(static_cast<uint32_t>(densMap.order.size()));
+    for (uint32_t d : densMap.order) {  // GaussDensityEstimator::write: mean index, covariance index
+        w.put<uint32_t>(static_cast<uint32_t>(meanMap.index[t.dnsMean[d]]));
+        w.put<uint32_t>(static_cast<uint32_t>(covMap.index[t.dnsCov[d]]));
+    }
+    w.put<uint32_t>(t.nMix);
+    for (uint32_t m = 0; m < t.nMix; ++m) {  // AbstractMixtureEstimator::write: count, then (density index, weight)
+        w.put<uint32_t>(t.mixOff[m + 1] - t.mixOff[m]);
+        for (uint32_t e = t.mixOff[m]; e < t.mixOff[m + 1]; ++e) {
+            w.put<uint32_t>(static_cast<uint32_t>(densMap.index[t.mixDens[e]]));
+            w.put<double>(t.entryWeights[e]);
+        }
+    }
+    return std::move(w.bytes);
+}
+
+}  // namespace rasr_gmm
 
 extern "C" {
 
@@ -354,6 +476,77 @@ int gmm_mixture_set_estimate(const void* data, uint64_t size, const gmm_estimato
         gmm_mixture_set_free(out);
         return fail(GMM_ERR_OUT_OF_MEMORY, "out of host memory");
     }
+    return GMM_OK;
+}
+
+int gmm_estimator_combine(const void* const* data, const uint64_t* size, uint32_t n, void* out, uint64_t capacity,
+                          uint64_t* outSize) {
+    if (!data || !size || !outSize)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "combine: no estimator files");
+    EstimatorFile sum;
+    for (uint32_t i = 0; i < n; ++i) {
+        EstimatorFile     f;
+        const std::string where = "combine: file " + std::to_string(i) + ": ";
+        const std::string err   = readEstimatorFile(data[i], size[i], f);
+        if (!err.empty())
+            return fail(GMM_ERR_INVALID_ARGUMENT, where + err);
+        if (i == 0) {  // the first file supplies the starting value
+            sum = std::move(f);
+            continue;
+        }
+        if (f.version != sum.version)
+            return fail(GMM_ERR_INVALID_ARGUMENT, where + "Different versions.");
+        if (f.dimension != sum.dimension)
+            return fail(GMM_ERR_INVALID_ARGUMENT, where + "Mismatch in dimension.");
+        if (f.means.size() != sum.means.size() || f.covs.size() != sum.covs.size() || f.dens.size() != sum.dens.size() ||
+            f.mix.size() != sum.mix.size())
+            return fail(GMM_ERR_INVALID_ARGUMENT, where + "Mismatch in number of means, covariances, densities or mixtures.");
+        for (size_t d = 0; d < f.dens.size(); ++d)  // accumulateDensity: equal mean and covariance indices
+            if (f.dens[d].mean != sum.dens[d].mean || f.dens[d].cov != sum.dens[d].cov)
+                return fail(GMM_ERR_INVALID_ARGUMENT, where + "density " + std::to_string(d) + " differs (topology mismatch)");
+        for (size_t m = 0; m < f.mix.size(); ++m)  // accumulateMixture: equal density indices
+            if (f.mix[m].dens != sum.mix[m].dens)
+                return fail(GMM_ERR_INVALID_ARGUMENT, where + "mixture " + std::to_string(m) + " differs (topology mismatch)");
+        // VectorAccumulator::operator+=: sum = sum + other, weight = weight + other
+        for (size_t a = 0; a < f.means.size() + f.covs.size(); ++a) {
+            Accumulator&       dst = a < f.means.size() ? sum.means[a] : sum.covs[a - f.means.size()];
+            const Accumulator& src = a < f.means.size() ? f.means[a] : f.covs[a - f.means.size()];
+            for (size_t k = 0; k < dst.sum.size(); ++k)
+                dst.sum[k] = dst.sum[k] + src.sum[k];
+            dst.weight = dst.weight + src.weight;
+        }
+        for (size_t m = 0; m < f.mix.size(); ++m)
+            for (size_t j = 0; j < f.mix[m].weights.size(); ++j)
+                sum.mix[m].weights[j] = sum.mix[m].weights[j] + f.mix[m].weights[j];
+    }
+    Writer w;
+    w.header(sum.dimension);
+    for (const std::vector<Accumulator>* accs : {&sum.means, &sum.covs}) {
+        w.put<uint32_t>(static_cast<uint32_t>(accs->size()));
+        for (const Accumulator& a : *accs)
+            w.accumulator(a.sum.data(), a.sum.size(), a.weight);
+    }
+    w.put<uint32_t>(static_cast<uint32_t>(sum.dens.size()));
+    for (const DensityEst& d : sum.dens) {
+        w.put<uint32_t>(d.mean);
+        w.put<uint32_t>(d.cov);
+    }
+    w.put<uint32_t>(static_cast<uint32_t>(sum.mix.size()));
+    for (const MixtureEst& x : sum.mix) {
+        w.put<uint32_t>(static_cast<uint32_t>(x.dens.size()));
+        for (size_t j = 0; j < x.dens.size(); ++j) {
+            w.put<uint32_t>(x.dens[j]);
+            w.put<double>(x.weights[j]);
+        }
+    }
+    *outSize = w.bytes.size();
+    if (!out)
+        return GMM_OK;
+    if (capacity < w.bytes.size())
+        return fail(GMM_ERR_CAPACITY, "combine: " + std::to_string(w.bytes.size()) + " bytes, capacity " + std::to_string(capacity));
+    std::memcpy(out, w.bytes.data(), w.bytes.size());
     return GMM_OK;
 }
 

@@ -1,0 +1,160 @@
+"""Python handle over the maximum-likelihood accumulation of include/rasr_gmm_estimator.h.
+
+`Estimator` turns aligned (frame, mixture) pairs into the f64 statistics of a mixture set on the GPU
+(AbstractMixtureSetEstimator::accumulate in Viterbi mode), writes them as a RASR estimator file and estimates
+the next mixture set; `combine_estimators` adds several such files (the trainer's combine action, host only).
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+
+import numpy as np
+
+from . import _capi
+from .mixture_set import MixtureSet, _from_desc, estimator_config
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+class Estimator:
+    """gmm_estimator: one accumulator per mean, covariance and mixture entry of `topology` (a MixtureSet, of which
+    only the dimension and the index tables are used) on one GPU, and the scratch of calls of up to max_pairs."""
+
+    def __init__(self, topology: MixtureSet, max_pairs: int, device: int = 0):
+        self._lib = _capi.load_library()
+        self.topology = topology
+        self.max_pairs = int(max_pairs)
+        self.device = int(device)
+        self._h = None
+        desc = topology.desc()
+        h = ctypes.c_void_p()
+        _capi.check(self._lib.gmm_estimator_create(ctypes.byref(desc), self.max_pairs, self.device, ctypes.byref(h)),
+                    "gmm_estimator_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.gmm_estimator_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def reset(self) -> None:
+        """Zeroes the tables and the skipped count."""
+        _capi.check(self._lib.gmm_estimator_reset(self._h), "gmm_estimator_reset")
+
+    def accumulate_device(self, frames, pair_frame, pair_mixture, pair_density=None, pair_weight=None, scorer=None,
+                          stream=None, n_frames=None) -> None:
+        """gmm_estimator_accumulate_device: frames torch cuda f32 [F, >=D]; pair_frame / pair_mixture / pair_density
+        int32 or uint32 cuda tensors of n_pairs; pair_weight a float64 cuda tensor or None (weight 1).  Without
+        pair_density the density is the scorer's best density of the pair (`scorer`: a Scorer), or, without a scorer,
+        the only density of the mixture.  Asynchronous on `stream` (torch stream or raw handle)."""
+        import torch
+        f = int(frames.shape[0] if n_frames is None else n_frames)
+        n = int(pair_frame.numel())
+        if frames.dtype != torch.float32 or frames.dim() != 2 or frames.stride(1) != 1:
+            raise ValueError("frames must be a float32 [F, >= D] tensor with unit column stride")
+        for name, t in (("pair_frame", pair_frame), ("pair_mixture", pair_mixture), ("pair_density", pair_density)):
+            if t is not None and (t.numel() != n or t.element_size() != 4 or t.dtype.is_floating_point
+                                  or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous int32 / uint32 tensor of n_pairs entries")
+        if pair_weight is not None and (pair_weight.numel() != n or pair_weight.dtype != torch.float64
+                                        or not pair_weight.is_contiguous()):
+            raise ValueError("pair_weight must be a contiguous float64 tensor of n_pairs entries")
+        if stream is None:
+            stream = torch.cuda.current_stream(frames.device)
+        s = getattr(stream, "cuda_stream", stream)
+
+        def p(t):
+            return None if t is None else ctypes.c_void_p(t.data_ptr())
+        rc = self._lib.gmm_estimator_accumulate_device(
+            self._h, scorer.handle if scorer is not None else None, p(frames), f, int(frames.stride(0)), p(pair_frame),
+            p(pair_mixture), p(pair_density), p(pair_weight), n, ctypes.c_void_p(s) if s else None)
+        _capi.check(rc, "gmm_estimator_accumulate_device")
+
+    def accumulate_host(self, frames, pair_frame, pair_mixture, pair_density=None, pair_weight=None, scorer=None) -> None:
+        """gmm_estimator_accumulate_host: the same call on numpy arrays, synchronous."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        if frames.ndim != 2:
+            raise ValueError("frames must be [F, >= D]")
+        pf = np.ascontiguousarray(pair_frame, dtype=np.uint32)
+        pm = np.ascontiguousarray(pair_mixture, dtype=np.uint32)
+        pd = None if pair_density is None else np.ascontiguousarray(pair_density, dtype=np.uint32)
+        pw = None if pair_weight is None else np.ascontiguousarray(pair_weight, dtype=np.float64)
+        n = pf.shape[0]
+        if pf.ndim != 1 or any(a is not None and a.shape != (n,) for a in (pm, pd, pw)):
+            raise ValueError("the pair arrays must be 1-d arrays of one length")
+        rc = self._lib.gmm_estimator_accumulate_host(
+            self._h, scorer.handle if scorer is not None else None, _ptr(frames), frames.shape[0], frames.shape[1],
+            _ptr(pf), _ptr(pm), _ptr(pd), _ptr(pw), n)
+        _capi.check(rc, "gmm_estimator_accumulate_host")
+
+    @property
+    def skipped(self) -> int:
+        """Pairs skipped since creation or the last reset (out-of-range frame, mixture or density, no best density)."""
+        v = ctypes.c_uint64()
+        _capi.check(self._lib.gmm_estimator_skipped(self._h, ctypes.byref(v)), "gmm_estimator_skipped")
+        return int(v.value)
+
+    def get(self) -> dict:
+        """The tables as f64 numpy arrays: mean_sums [n_means, D], mean_weights [n_means], covariance_sums
+        [n_covariances, D], covariance_weights [n_covariances], entry_weights [n_entries]."""
+        t = self.topology
+        D = t.dimension
+        out = {"mean_sums": np.zeros((t.means.shape[0], D), np.float64),
+               "mean_weights": np.zeros(t.means.shape[0], np.float64),
+               "covariance_sums": np.zeros((t.n_covariances, D), np.float64),
+               "covariance_weights": np.zeros(t.n_covariances, np.float64),
+               "entry_weights": np.zeros(t.n_entries, np.float64)}
+        _capi.check(self._lib.gmm_estimator_get(self._h, _ptr(out["mean_sums"]), _ptr(out["mean_weights"]),
+                                                _ptr(out["covariance_sums"]), _ptr(out["covariance_weights"]),
+                                                _ptr(out["entry_weights"])), "gmm_estimator_get")
+        return out
+
+    def to_bytes(self) -> bytes:
+        """gmm_estimator_serialize: the estimator file AbstractMixtureSetEstimator::write produces."""
+        size = ctypes.c_uint64()
+        _capi.check(self._lib.gmm_estimator_serialize(self._h, None, 0, ctypes.byref(size)), "gmm_estimator_serialize")
+        buf = ctypes.create_string_buffer(max(int(size.value), 1))
+        _capi.check(self._lib.gmm_estimator_serialize(self._h, buf, size.value, ctypes.byref(size)),
+                    "gmm_estimator_serialize")
+        return buf.raw[:size.value]
+
+    def write(self, path) -> None:
+        _capi.check(self._lib.gmm_estimator_write(self._h, os.fsencode(path)), "gmm_estimator_write")
+
+    def estimate(self, **estimator) -> MixtureSet:
+        """gmm_estimator_estimate: the mixture set estimated from the tables (keywords: estimator_config)."""
+        d = _capi.MixtureSetDesc()
+        cfg = estimator_config(**estimator)
+        _capi.check(self._lib.gmm_estimator_estimate(self._h, ctypes.byref(cfg), ctypes.byref(d)), "gmm_estimator_estimate")
+        try:
+            return _from_desc(d)
+        finally:
+            self._lib.gmm_mixture_set_free(ctypes.byref(d))
+
+
+def combine_estimators(files) -> bytes:
+    """gmm_estimator_combine: the bytes of several estimator files of one topology added in order (host only)."""
+    lib = _capi.load_library()
+    files = [bytes(f) for f in files]
+    n = len(files)
+    bufs = [ctypes.create_string_buffer(f, max(len(f), 1)) for f in files]
+    data = (ctypes.c_void_p * max(n, 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
+    sizes = (ctypes.c_uint64 * max(n, 1))(*[len(f) for f in files])
+    size = ctypes.c_uint64()
+    _capi.check(lib.gmm_estimator_combine(data, sizes, n, None, 0, ctypes.byref(size)), "gmm_estimator_combine")
+    out = ctypes.create_string_buffer(max(int(size.value), 1))
+    _capi.check(lib.gmm_estimator_combine(data, sizes, n, out, size.value, ctypes.byref(size)), "gmm_estimator_combine")
+    return out.raw[:size.value]
