@@ -26,7 +26,7 @@ OBJS      = $(BUILD)/gmm_kernels_i8.o $(BUILD)/gmm_kernels_f32.o $(BUILD)/gmm_ke
             $(BUILD)/gmm_kernels_presel.o $(BUILD)/gmm_presel.o $(BUILD)/gmm_kernels_shard.o $(BUILD)/gmm_hostio.o \
             $(BUILD)/gmm_kernels_direct.o $(BUILD)/gmm_kernels_layout.o $(BUILD)/gmm_shard.o $(BUILD)/gmm_kernels_pairs.o \
             $(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o \
-            $(BUILD)/gmm_kernels_accum.o $(BUILD)/gmm_estimator.o
+            $(BUILD)/gmm_kernels_accum.o $(BUILD)/gmm_estimator.o $(BUILD)/gmm_kernels_posterior.o
 # include/rasr_gmm_estimator.h: the units behind it depend on these besides HDRS
 EST_HDRS  = include/rasr_gmm_estimator.h $(SRC)/gmm_estimator.hh
 DRIVER    = $(BUILD)/tests/feature_scorer_driver
@@ -62,6 +62,12 @@ $(BUILD)/gmm_kernels_direct.o: $(SRC)/gmm_kernels_direct.hip $(HDRS)
 
 # sparse best densities of (frame, mixture) pairs (gmm_best_density_pairs): the reference's scalar order
 $(BUILD)/gmm_kernels_pairs.o: $(SRC)/gmm_kernels_pairs.hip $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
+
+# density posteriors of (frame, mixture) pairs and their Baum-Welch expansion (gmm_density_posteriors_pairs_*,
+# gmm_estimator_accumulate_posteriors_*): the reference's scalar order, as gmm_kernels_pairs.  Not one of KERNEL_OBJS
+$(BUILD)/gmm_kernels_posterior.o: $(SRC)/gmm_kernels_posterior.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
 

@@ -238,6 +238,36 @@ int gmm_best_density_pairs_device(gmm_scorer* scorer, const float* frames, uint3
                                   const uint32_t* pair_frame, const uint32_t* pair_mixture, uint32_t n_pairs,
                                   uint32_t* best_density, void* stream);
 
+/* Density posteriors of (frame, mixture) pairs: GaussDiagonalSumFeatureScorer::calculateDensityPosteriorProbabilities
+ * (GaussDiagonalMaximumFeatureScorer.cc:291-298) with score(e) of cc:263-289 as the log denominator, the call
+ * AbstractMixtureSetEstimator::getDensityPosteriorProbabilities (cc:386-402) makes in Baum-Welch mode.  Pointers,
+ * stream and pair rules as gmm_best_density_pairs_device: all DEVICE pointers, enqueued on `stream`, asynchronous.
+ * Per pair (f, m) with n the entry count of mixture m, every f32 operation rounded once and nothing fused:
+ *     s_j     the density scores of the diagonal-sum best-density kernel: 0.5f * ((w_j + logNorm_cov) + distance_j),
+ *             from the handle's own tables (its mixture-weight and Gaussian scales are in; score_scale is NOT applied:
+ *             the reference's estimator holds the unscaled assigning scorer)
+ *     best    the strict-compare scan (best > s_j) in entry order from FLT_MAX
+ *     sumExp  0, then sumExp + expf(best - s_j) in entry order
+ *     logDen  best - logf(sumExp)
+ *     post_j  expf(logDen - s_j)
+ * with the device library's expf / logf.  The order is fixed (one wave per pair), so the call is deterministic bit
+ * for bit.  posteriors[p * row_stride + j] = post_j for j < n and 0 for n <= j < row_stride; log_denominator[p] =
+ * logDen (the pointer may be NULL).  A pair whose frame or mixture is out of range, or whose mixture is empty, gets
+ * a row of zeros and +inf, and its frame is never read; a pair without a finite score gets what the arithmetic gives.
+ * Errors: GMM_ERR_UNSUPPORTED for every type but diagonal-sum (in the reference only that class implements the call,
+ * the base reports a critical error, AssigningFeatureScorer.hh:135-138) and where gmm_best_density_pairs_device is
+ * unsupported; GMM_ERR_CAPACITY for row_stride below the largest entry count of the handle's mixtures;
+ * GMM_ERR_INVALID_ARGUMENT for frame_stride below the dimension. */
+int gmm_density_posteriors_pairs_device(gmm_scorer* scorer, const float* frames, uint32_t n_frames,
+                                        uint32_t frame_stride, const uint32_t* pair_frame, const uint32_t* pair_mixture,
+                                        uint32_t n_pairs, float* posteriors, uint32_t row_stride, float* log_denominator,
+                                        void* stream);
+
+/* The same call with HOST arrays: stages them through device memory and is synchronous. */
+int gmm_density_posteriors_pairs_host(gmm_scorer* scorer, const float* frames, uint32_t n_frames, uint32_t frame_stride,
+                                      const uint32_t* pair_frame, const uint32_t* pair_mixture, uint32_t n_pairs,
+                                      float* posteriors, uint32_t row_stride, float* log_denominator);
+
 /* Page-locked host memory for gmm_score_host's outputs (the buffer a batched caller keeps, e.g.
  * BatchFeatureScorerBase::scores_, BatchFeatureScorer.hh:177-186), so that callers need no HIP
  * headers.  gmm_host_free(NULL) is a no-op. */

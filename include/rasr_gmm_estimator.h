@@ -1,11 +1,12 @@
 /*
- * rasr_gmm_estimator.h -- maximum-likelihood (Viterbi) accumulation for mixture-set training (C-ABI).
+ * rasr_gmm_estimator.h -- maximum-likelihood accumulation (Viterbi and Baum-Welch) for mixture-set training (C-ABI).
  *
  * The step between an alignment and the next model: aligned (frame, mixture) pairs are accumulated into the
  * f64 statistics of the mixture set's means, covariances and mixture weights ON THE DEVICE, written in the
  * format of RASR's binary estimator files, combined, and estimated (rasr_gmm_io.h).  Replaces
  *   AbstractMixtureSetEstimator::setTopology            src/Mm/AbstractMixtureSetEstimator.cc:78-115
  *   AbstractMixtureSetEstimator::accumulate (Viterbi)   src/Mm/AbstractMixtureSetEstimator.cc:117-131
+ *   AbstractMixtureSetEstimator::accumulate (Baum-Welch) src/Mm/AbstractMixtureSetEstimator.cc:127-147, 386-402
  *   AbstractMixtureSetEstimator::densityIndex           src/Mm/AbstractMixtureSetEstimator.cc:370-384
  *   AbstractMixtureEstimator::accumulate                src/Mm/MixtureEstimator.cc (weights_[index] += weight)
  *   GaussDensityEstimator::accumulate                   src/Mm/GaussDensityEstimator.cc (mean, then covariance)
@@ -13,7 +14,8 @@
  *   AbstractMixtureSetEstimator::write                  src/Mm/AbstractMixtureSetEstimator.cc:416-420, 481-509
  *   MixtureSetEstimatorIndexMap                         src/Mm/AbstractMixtureSetEstimator.cc:804-817
  *   accumulate(Core::BinaryInputStreams&, os)           src/Mm/AbstractMixtureSetEstimator.cc:171-290 (combine)
- * Not covered: Baum-Welch mode (density posteriors, cc:132-146) and the discriminative estimators.
+ * Not covered: the trainer's logging statistics (weightStats_, dnsPosteriorStats_, finalWeightStats_,
+ * scoreStatistics_) and the discriminative estimators.
  *
  * THE NUMERIC CONTRACT: deterministic order, no floating-point atomics.
  * An accumulator (one mean, one covariance, one mixture entry) that receives n <= GMM_ESTIMATOR_CHUNK
@@ -50,7 +52,8 @@ typedef struct gmm_estimator gmm_estimator;
  * `topology` (only its dimension and index tables are used, means / variances / log weights may be NULL), as zeroed
  * f64 tables on `device`: mean sums [n_means][D], mean weights [n_means], covariance sums [n_covariances][D],
  * covariance weights [n_covariances], mixture-entry weights [n_entries]; and the scratch of a call of up to
- * max_pairs pairs.  GMM_ERR_INVALID_ARGUMENT for indices out of range. */
+ * max_pairs pairs (for gmm_estimator_accumulate_posteriors_*: of up to max_pairs CONTRIBUTIONS, see there).
+ * GMM_ERR_INVALID_ARGUMENT for indices out of range. */
 int gmm_estimator_create(const gmm_mixture_set* topology, uint32_t max_pairs, int device, gmm_estimator** out);
 int gmm_estimator_destroy(gmm_estimator* estimator);
 
@@ -87,6 +90,44 @@ int gmm_estimator_accumulate_host(gmm_estimator* estimator, gmm_scorer* scorer, 
                                   uint32_t n_frames, uint32_t frame_stride, const uint32_t* pair_frame,
                                   const uint32_t* pair_mixture, const uint32_t* pair_density,
                                   const double* pair_weight, uint32_t n_pairs);
+
+/* AbstractMixtureSetEstimator::weightThreshold_ = Core::Type<f32>::epsilon (cc:63; src/Core/Types.hh:148:
+ * 1.19209290e-07F, i.e. 2^-23 = FLT_EPSILON), widened to the f64 it is compared in */
+#define GMM_ESTIMATOR_DEFAULT_WEIGHT_THRESHOLD 1.1920928955078125e-07
+
+/* accumulate(mixtureIndex, featureVector, weight) in Baum-Welch mode (cc:127-147, 386-402) for a list of pairs: pair
+ * i is spread over ALL densities of mixture pair_mixture[i] by their posterior probabilities.  It expands into the
+ * contributions (i, j), one per density j of the mixture, with
+ *     finalWeight = pair_weight[i] * (double) post_ij      (one f64 multiply; NULL pair_weight: 1)
+ * where post_ij is the f32 posterior of gmm_density_posteriors_pairs_device for that pair, bit for bit.  A
+ * contribution is accumulated iff finalWeight > weight_threshold (a strict f64 compare; NaN does not pass), and then
+ * adds exactly as a Viterbi pair of weight finalWeight on density j does: to the entry weight, the mean sums and the
+ * covariance squared sums.  Without a scorer (scorer == NULL) every mixture must hold exactly one density
+ * (GMM_ERR_INVALID_ARGUMENT otherwise, the verify_ at cc:398): its posterior is 1.0 and the threshold still applies.
+ * ORDER: the contributions of a call are ordered by (pair index, density in mixture), the reference's loop order, and
+ * the numeric contract at the top of this file holds for that list as it does for a Viterbi call's pairs: every
+ * accumulator sequentially in f64 in contribution order, pieces of GMM_ESTIMATOR_CHUNK, no floating-point atomics.
+ * CAPACITY: a call needs n_pairs * K_max <= max_pairs, K_max the largest entry count of the topology's mixtures (at
+ * least 1; 1 without a scorer), the product taken in 64 bits: max_pairs counts contribution slots for this call.
+ * GMM_ERR_CAPACITY otherwise.
+ * SKIPPED: a pair is skipped and counted once when its frame or mixture is out of range or its mixture is empty; its
+ * data are never touched.  A pair whose contributions all stay under the threshold is not skipped.
+ * The other errors are gmm_estimator_accumulate_device's, and GMM_ERR_UNSUPPORTED for every scorer type but
+ * diagonal-sum (gmm_density_posteriors_pairs_device).  A refused call changes neither the tables nor the count.
+ * All pointers are DEVICE pointers; the call is enqueued on `stream` and does not synchronize the host.  The
+ * handle's FIRST posterior call allocates the posterior scratch (the rows, the contributions' frames and weights:
+ * max_pairs elements each), which the handle keeps: handles that only see Viterbi calls never pay for it, and later
+ * calls allocate nothing.  The posterior and Viterbi calls may be mixed on one handle, under the same one-stream rule. */
+int gmm_estimator_accumulate_posteriors_device(gmm_estimator* estimator, gmm_scorer* scorer, const float* frames,
+                                               uint32_t n_frames, uint32_t frame_stride, const uint32_t* pair_frame,
+                                               const uint32_t* pair_mixture, const double* pair_weight, uint32_t n_pairs,
+                                               double weight_threshold, void* stream);
+
+/* The same call with HOST arrays: copies them in and is synchronous. */
+int gmm_estimator_accumulate_posteriors_host(gmm_estimator* estimator, gmm_scorer* scorer, const float* frames,
+                                             uint32_t n_frames, uint32_t frame_stride, const uint32_t* pair_frame,
+                                             const uint32_t* pair_mixture, const double* pair_weight, uint32_t n_pairs,
+                                             double weight_threshold);
 
 /* Pairs skipped since creation or the last reset.  Waits for the last accumulate call. */
 int gmm_estimator_skipped(gmm_estimator* estimator, uint64_t* skipped);

@@ -162,7 +162,9 @@ int setupPairs(gmm_scorer* s, const gmm_mixture_set& ms, ShardRange shard, const
     if ((rc = upload(t->dMixOff, mixOff)) || (rc = upload(t->dCov, cov)))
         return rc;
     t->nEntries = ee - eb;
-    s->pairs    = std::move(t);
+    for (size_t m = 0; m + 1 < mixOff.size(); ++m)
+        t->maxEntries = std::max(t->maxEntries, mixOff[m + 1] - mixOff[m]);
+    s->pairs = std::move(t);
     return GMM_OK;
 }
 

@@ -30,6 +30,13 @@ struct gmm_estimator {
     // the host call's pair lists
     DeviceBuffer<uint32_t> dPairFrame, dPairMix, dPairDensity;
     DeviceBuffer<double>   dPairWeight;
+    // Baum-Welch calls: the posterior rows and the contributions' frames and weights, maxPairs elements each,
+    // allocated by the handle's first posterior call
+    uint32_t               maxEntries = 1;  // K_max: the largest entry count of a mixture (at least 1)
+    bool                   posteriorScratch = false;
+    DeviceBuffer<float>    dPostRows;
+    DeviceBuffer<uint32_t> dContribFrame;
+    DeviceBuffer<double>   dContribWeight;
     // recorded by every accumulate call on its stream; get / skipped / serialize wait for it
     Event done;
     bool  pending = false;
@@ -104,8 +111,10 @@ int create(gmm_estimator* e, const gmm_mixture_set& ms, uint32_t maxPairs, int d
         entryCov[i]  = e->dnsCov[e->mixDens[i]];
     }
     e->oneDensityPerMixture = true;
-    for (uint32_t m = 0; m < e->nMix; ++m)
+    for (uint32_t m = 0; m < e->nMix; ++m) {
         e->oneDensityPerMixture = e->oneDensityPerMixture && e->mixOff[m + 1] - e->mixOff[m] == 1;
+        e->maxEntries           = std::max(e->maxEntries, e->mixOff[m + 1] - e->mixOff[m]);
+    }
 
     GMM_HIP_CHECK(hipSetDevice(device));
     int rc;
@@ -170,40 +179,11 @@ int checkCall(const gmm_estimator* e, const gmm_scorer* scorer, const float* fra
     return GMM_OK;
 }
 
-int accumulateOn(gmm_estimator* e, gmm_scorer* scorer, const float* frames, uint32_t nFrames, uint32_t frameStride,
-                 const uint32_t* pairFrame, const uint32_t* pairMix, const uint32_t* pairDensity,
-                 const double* pairWeight, uint32_t nPairs, hipStream_t stream) {
-    if (nPairs == 0)
-        return GMM_OK;
-    if (!pairDensity && scorer) {  // the Viterbi branch: densityIndex() = bestDensity of the pair
-        PairArgs a  = pairArgsOf(scorer, frames, nFrames, frameStride);
-        a.pairFrame = pairFrame;
-        a.pairMix   = pairMix;
-        a.best      = e->dBest.get();
-        a.nPairs    = nPairs;
-        GMM_HIP_CHECK(launchBestPairs(a, stream));
-        pairDensity = e->dBest.get();
-    }
-    ResolveArgs r{};
-    r.pairFrame   = pairFrame;
-    r.pairMix     = pairMix;
-    r.pairDensity = pairDensity;
-    r.mixOff      = e->dMixOff.get();
-    r.entryMean   = e->dEntryMean.get();
-    r.entryCov    = e->dEntryCov.get();
-    r.keyMean     = e->dKeyMean.get();
-    r.keyCov      = e->dKeyCov.get();
-    r.keyEntry    = e->dKeyEntry.get();
-    r.pairIndex   = e->dPairIndex.get();
-    r.skipped     = e->dSkipped.get();
-    r.nPairs      = nPairs;
-    r.nFrames     = nFrames;
-    r.nMix        = e->nMix;
-    r.nMeans      = e->nMeans;
-    r.nCovs       = e->nCovs;
-    r.nEntries    = e->nEntries;
-    GMM_HIP_CHECK(static_cast<hipError_t>(launchResolvePairs(r, stream)));
-
+// the three inverted indexes of a call whose keys are written (dKeyMean / dKeyCov / dKeyEntry, dPairIndex = 0, 1, ...):
+// per index the stable sort, the ordered sums of the pieces, the pieces' combination.  n contributions; pairFrame and
+// pairWeight are indexed by contribution
+int accumulateKeyed(gmm_estimator* e, const float* frames, uint32_t frameStride, const uint32_t* pairFrame,
+                    const double* pairWeight, uint32_t nPairs, hipStream_t stream) {
     AccumArgs a{};
     a.keysSorted  = e->dKeysSorted.get();
     a.indexSorted = e->dIndexSorted.get();
@@ -238,6 +218,106 @@ int accumulateOn(gmm_estimator* e, gmm_scorer* scorer, const float* frames, uint
         GMM_HIP_CHECK(static_cast<hipError_t>(launchCombinePieces(a, stream)));
     }
     return GMM_OK;
+}
+
+int accumulateOn(gmm_estimator* e, gmm_scorer* scorer, const float* frames, uint32_t nFrames, uint32_t frameStride,
+                 const uint32_t* pairFrame, const uint32_t* pairMix, const uint32_t* pairDensity,
+                 const double* pairWeight, uint32_t nPairs, hipStream_t stream) {
+    if (nPairs == 0)
+        return GMM_OK;
+    if (!pairDensity && scorer) {  // the Viterbi branch: densityIndex() = bestDensity of the pair
+        PairArgs a  = pairArgsOf(scorer, frames, nFrames, frameStride);
+        a.pairFrame = pairFrame;
+        a.pairMix   = pairMix;
+        a.best      = e->dBest.get();
+        a.nPairs    = nPairs;
+        GMM_HIP_CHECK(launchBestPairs(a, stream));
+        pairDensity = e->dBest.get();
+    }
+    ResolveArgs r{};
+    r.pairFrame   = pairFrame;
+    r.pairMix     = pairMix;
+    r.pairDensity = pairDensity;
+    r.mixOff      = e->dMixOff.get();
+    r.entryMean   = e->dEntryMean.get();
+    r.entryCov    = e->dEntryCov.get();
+    r.keyMean     = e->dKeyMean.get();
+    r.keyCov      = e->dKeyCov.get();
+    r.keyEntry    = e->dKeyEntry.get();
+    r.pairIndex   = e->dPairIndex.get();
+    r.skipped     = e->dSkipped.get();
+    r.nPairs      = nPairs;
+    r.nFrames     = nFrames;
+    r.nMix        = e->nMix;
+    r.nMeans      = e->nMeans;
+    r.nCovs       = e->nCovs;
+    r.nEntries    = e->nEntries;
+    GMM_HIP_CHECK(static_cast<hipError_t>(launchResolvePairs(r, stream)));
+    return accumulateKeyed(e, frames, frameStride, pairFrame, pairWeight, nPairs, stream);
+}
+
+// the checks of a posterior call that need no device: checkCall's, diagonal-sum only, contribution slots
+int checkPosteriorCall(const gmm_estimator* e, const gmm_scorer* scorer, const float* frames, uint32_t frameStride,
+                       const uint32_t* pairFrame, const uint32_t* pairMix, uint32_t nPairs) {
+    if (!e)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null estimator");
+    // n_pairs <= n_pairs * K_max: checkCall's own capacity check cannot fire before this one
+    const uint64_t slots = static_cast<uint64_t>(nPairs) * (scorer ? e->maxEntries : 1u);
+    if (slots > e->maxPairs)
+        return fail(GMM_ERR_CAPACITY, std::to_string(nPairs) + " pairs of up to " + std::to_string(scorer ? e->maxEntries : 1u) +
+                                              " densities exceed the estimator's max_pairs " + std::to_string(e->maxPairs) +
+                                              " (contribution slots for this call)");
+    int rc = checkCall(e, scorer, frames, frameStride, pairFrame, pairMix, nullptr, nPairs);
+    if (rc == GMM_OK && scorer)
+        rc = checkPosteriors(scorer);
+    return rc;
+}
+
+// the posterior scratch, on the handle's first posterior call
+int ensurePosteriorScratch(gmm_estimator* e) {
+    if (e->posteriorScratch)
+        return GMM_OK;
+    GMM_HIP_CHECK(e->dPostRows.alloc(e->maxPairs));
+    GMM_HIP_CHECK(e->dContribFrame.alloc(e->maxPairs));
+    GMM_HIP_CHECK(e->dContribWeight.alloc(e->maxPairs));
+    e->posteriorScratch = true;
+    return GMM_OK;
+}
+
+// the Baum-Welch call: posteriors and expansion into contribution slots (one kernel), then the keyed tail over them
+int accumulatePosteriorsOn(gmm_estimator* e, gmm_scorer* scorer, const float* frames, uint32_t nFrames,
+                           uint32_t frameStride, const uint32_t* pairFrame, const uint32_t* pairMix,
+                           const double* pairWeight, uint32_t nPairs, double threshold, hipStream_t stream) {
+    PosteriorArgs q{};
+    if (scorer)
+        q.pair = pairArgsOf(scorer, frames, nFrames, frameStride);
+    else {
+        q.pair.nFrames   = nFrames;
+        q.pair.nMixtures = e->nMix;
+        q.pair.mixOff    = e->dMixOff.get();
+    }
+    q.pair.pairFrame = pairFrame;
+    q.pair.pairMix   = pairMix;
+    q.pair.nPairs    = nPairs;
+    q.posteriors     = e->dPostRows.get();
+    q.rowStride      = scorer ? e->maxEntries : 1u;
+    q.pairWeight     = pairWeight;
+    q.threshold      = threshold;
+    q.entryMean      = e->dEntryMean.get();
+    q.entryCov       = e->dEntryCov.get();
+    q.keyMean        = e->dKeyMean.get();
+    q.keyCov         = e->dKeyCov.get();
+    q.keyEntry       = e->dKeyEntry.get();
+    q.contribIndex   = e->dPairIndex.get();
+    q.contribFrame   = e->dContribFrame.get();
+    q.contribWeight  = e->dContribWeight.get();
+    q.skipped        = e->dSkipped.get();
+    q.nMeans         = e->nMeans;
+    q.nCovs          = e->nCovs;
+    q.nEntries       = e->nEntries;
+    GMM_HIP_CHECK(scorer ? launchDensityPosteriors(q, stream) : launchExpandSingleDensity(q, stream));
+    return accumulateKeyed(e, frames, frameStride, e->dContribFrame.get(), e->dContribWeight.get(), nPairs * q.rowStride,
+                           stream);
 }
 
 // host copies of the tables, after the last call
@@ -371,6 +451,47 @@ int gmm_estimator_accumulate_host(gmm_estimator* e, gmm_scorer* scorer, const fl
     rc = accumulateOn(e, scorer, dFrames.get(), nFrames, e->D, e->dPairFrame.get(), e->dPairMix.get(),
                       pairDensity ? e->dPairDensity.get() : nullptr, pairWeight ? e->dPairWeight.get() : nullptr, nPairs,
                       nullptr);
+    GMM_HIP_CHECK(hipStreamSynchronize(nullptr));  // before dFrames is released
+    return rc;
+}
+
+int gmm_estimator_accumulate_posteriors_device(gmm_estimator* e, gmm_scorer* scorer, const float* frames, uint32_t nFrames,
+                                               uint32_t frameStride, const uint32_t* pairFrame, const uint32_t* pairMix,
+                                               const double* pairWeight, uint32_t nPairs, double threshold, void* stream) {
+    int rc = checkPosteriorCall(e, scorer, frames, frameStride, pairFrame, pairMix, nPairs);
+    if (rc != GMM_OK || nPairs == 0)
+        return rc;
+    GMM_HIP_CHECK(hipSetDevice(e->device));
+    if ((rc = ensurePosteriorScratch(e)) != GMM_OK)
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc             = accumulatePosteriorsOn(e, scorer, frames, nFrames, frameStride, pairFrame, pairMix, pairWeight, nPairs, threshold, st);
+    GMM_HIP_CHECK(hipEventRecord(e->done.get(), st));
+    e->pending = true;
+    return rc;
+}
+
+int gmm_estimator_accumulate_posteriors_host(gmm_estimator* e, gmm_scorer* scorer, const float* frames, uint32_t nFrames,
+                                             uint32_t frameStride, const uint32_t* pairFrame, const uint32_t* pairMix,
+                                             const double* pairWeight, uint32_t nPairs, double threshold) {
+    int rc = checkPosteriorCall(e, scorer, frames, frameStride, pairFrame, pairMix, nPairs);
+    if (rc != GMM_OK || nPairs == 0)
+        return rc;
+    GMM_HIP_CHECK(hipSetDevice(e->device));
+    if ((rc = waitDone(e)) != GMM_OK || (rc = ensurePosteriorScratch(e)) != GMM_OK)
+        return rc;
+    DeviceBuffer<float> dFrames;
+    const size_t        D = e->D, n = nPairs;
+    GMM_HIP_CHECK(dFrames.alloc(std::max<size_t>(static_cast<size_t>(nFrames) * D, 1)));
+    if (nFrames && D)
+        GMM_HIP_CHECK(hipMemcpy2D(dFrames.get(), D * sizeof(float), frames, static_cast<size_t>(frameStride) * sizeof(float),
+                                  D * sizeof(float), nFrames, hipMemcpyHostToDevice));
+    GMM_HIP_CHECK(hipMemcpy(e->dPairFrame.get(), pairFrame, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    GMM_HIP_CHECK(hipMemcpy(e->dPairMix.get(), pairMix, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (pairWeight)
+        GMM_HIP_CHECK(hipMemcpy(e->dPairWeight.get(), pairWeight, n * sizeof(double), hipMemcpyHostToDevice));
+    rc = accumulatePosteriorsOn(e, scorer, dFrames.get(), nFrames, e->D, e->dPairFrame.get(), e->dPairMix.get(),
+                                pairWeight ? e->dPairWeight.get() : nullptr, nPairs, threshold, nullptr);
     GMM_HIP_CHECK(hipStreamSynchronize(nullptr));  // before dFrames is released
     return rc;
 }

@@ -450,9 +450,93 @@ int checkPairs(const gmm_scorer* s) {
                                          "float model of dimension > 128): use gmm_fetch_best_density");
     return GMM_OK;
 }
+
+int checkPosteriors(const gmm_scorer* s) {
+    const int rc = checkPairs(s);
+    if (rc != GMM_OK)
+        return rc;
+    if (s->pairs->kind != kPairDiagonalSum)  // the base class's criticalError, AssigningFeatureScorer.hh:135-138
+        return fail(GMM_ERR_UNSUPPORTED, "density posteriors are defined for the diagonal-sum scorer only");
+    return GMM_OK;
+}
 }  // namespace rasr_gmm
 
+namespace {
+// the checks of gmm_density_posteriors_pairs_* that need no device
+int checkPosteriorCall(const gmm_scorer* s, const float* frames, uint32_t frameStride, const uint32_t* pairFrame,
+                       const uint32_t* pairMixture, uint32_t nPairs, const float* posteriors, uint32_t rowStride) {
+    if (!s || (nPairs && (!frames || !pairFrame || !pairMixture || !posteriors)))
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null argument");
+    const int rc = checkPosteriors(s);
+    if (rc != GMM_OK)
+        return rc;
+    if (frameStride < s->D)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "frame_stride below the dimension");
+    if (rowStride < s->pairs->maxEntries)
+        return fail(GMM_ERR_CAPACITY, "row_stride " + std::to_string(rowStride) + " below the largest mixture's " +
+                                              std::to_string(s->pairs->maxEntries) + " entries");
+    return GMM_OK;
+}
+}  // namespace
+
 extern "C" {
+
+int gmm_density_posteriors_pairs_device(gmm_scorer* s, const float* frames, uint32_t nFrames, uint32_t frameStride,
+                                        const uint32_t* pairFrame, const uint32_t* pairMixture, uint32_t nPairs,
+                                        float* posteriors, uint32_t rowStride, float* logDenominator, void* stream) {
+    const int rc = checkPosteriorCall(s, frames, frameStride, pairFrame, pairMixture, nPairs, posteriors, rowStride);
+    if (rc != GMM_OK || nPairs == 0)
+        return rc;
+    GMM_HIP_CHECK(hipSetDevice(s->device));
+    PosteriorArgs a{};
+    a.pair           = pairArgsOf(s, frames, nFrames, frameStride);
+    a.pair.pairFrame = pairFrame;
+    a.pair.pairMix   = pairMixture;
+    a.pair.nPairs    = nPairs;
+    a.posteriors     = posteriors;
+    a.logDen         = logDenominator;
+    a.rowStride      = rowStride;
+    GMM_HIP_CHECK(launchDensityPosteriors(a, static_cast<hipStream_t>(stream)));
+    return GMM_OK;
+}
+
+int gmm_density_posteriors_pairs_host(gmm_scorer* s, const float* frames, uint32_t nFrames, uint32_t frameStride,
+                                      const uint32_t* pairFrame, const uint32_t* pairMixture, uint32_t nPairs,
+                                      float* posteriors, uint32_t rowStride, float* logDenominator) {
+    const int rc = checkPosteriorCall(s, frames, frameStride, pairFrame, pairMixture, nPairs, posteriors, rowStride);
+    if (rc != GMM_OK || nPairs == 0)
+        return rc;
+    GMM_HIP_CHECK(hipSetDevice(s->device));
+    // the frames, dense (row length D); the pair lists; the rows
+    const size_t           D = s->D, n = nPairs, rows = n * rowStride;
+    DeviceBuffer<float>    dFrames, dPost, dLogDen;
+    DeviceBuffer<uint32_t> dPairs;
+    GMM_HIP_CHECK(dFrames.alloc(std::max<size_t>(static_cast<size_t>(nFrames) * D, 1)));
+    GMM_HIP_CHECK(dPairs.alloc(2 * n));
+    GMM_HIP_CHECK(dPost.alloc(std::max<size_t>(rows, 1)));
+    GMM_HIP_CHECK(dLogDen.alloc(n));
+    if (nFrames && D)
+        GMM_HIP_CHECK(hipMemcpy2D(dFrames.get(), D * sizeof(float), frames, static_cast<size_t>(frameStride) * sizeof(float),
+                                  D * sizeof(float), nFrames, hipMemcpyHostToDevice));
+    GMM_HIP_CHECK(hipMemcpy(dPairs.get(), pairFrame, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    GMM_HIP_CHECK(hipMemcpy(dPairs.get() + n, pairMixture, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    PosteriorArgs a{};
+    a.pair           = pairArgsOf(s, dFrames.get(), nFrames, s->D);
+    a.pair.pairFrame = dPairs.get();
+    a.pair.pairMix   = dPairs.get() + n;
+    a.pair.nPairs    = nPairs;
+    a.posteriors     = dPost.get();
+    a.logDen         = dLogDen.get();
+    a.rowStride      = rowStride;
+    GMM_HIP_CHECK(launchDensityPosteriors(a, nullptr));
+    // the copies on the default stream wait for the kernel and are synchronous: the buffers may go afterwards
+    if (rows)
+        GMM_HIP_CHECK(hipMemcpy(posteriors, dPost.get(), rows * sizeof(float), hipMemcpyDeviceToHost));
+    if (logDenominator)
+        GMM_HIP_CHECK(hipMemcpy(logDenominator, dLogDen.get(), n * sizeof(float), hipMemcpyDeviceToHost));
+    GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
+    return GMM_OK;
+}
 
 int gmm_best_density_pairs(gmm_scorer* s, uint64_t callId, const uint32_t* positions, const uint32_t* mixtures,
                            uint32_t nPairs, uint32_t* best) {

@@ -254,6 +254,34 @@ struct PairArgs {
     int             kind;        // PairKind
 };
 hipError_t launchBestPairs(const PairArgs& a, hipStream_t stream);
+
+// density posteriors of (frame, mixture) pairs (gmm_density_posteriors_pairs_*, gmm_kernels_posterior.hip): one wave
+// per pair, the diagonal-sum density scores of bestPairs, the reference's scan, sum and exponentials in entry order.
+// With keyMean != NULL the kernel's tail also expands the pair into the Baum-Welch contributions of
+// gmm_estimator_accumulate_posteriors_*: slot c = pair * rowStride + j for density j of the mixture
+struct PosteriorArgs {
+    PairArgs  pair;         // frames, pair lists and the diagonal-sum tables (pair.best is not used)
+    float*    posteriors;   // [nPairs][rowStride]: post_j, 0 from the mixture's entry count on
+    float*    logDen;       // [nPairs] or NULL: +inf for a pair out of range or on an empty mixture
+    uint32_t  rowStride;    // >= the largest mixture's entry count
+    // the expansion (all unused with keyMean == NULL)
+    const double*   pairWeight;    // [nPairs] or NULL: 1
+    double          threshold;     // a contribution is live iff pairWeight * (f64) post > threshold
+    const uint32_t* entryMean;     // [nEntries] the estimator's tables
+    const uint32_t* entryCov;      // [nEntries]
+    uint32_t*       keyMean;       // [nPairs * rowStride] out: the destination, or the sentinel (the destination count)
+    uint32_t*       keyCov;        // for a slot past the mixture's entries, of a bad pair or under the threshold
+    uint32_t*       keyEntry;
+    uint32_t*       contribIndex;  // [nPairs * rowStride] out: 0, 1, ... (the sorts' values)
+    uint32_t*       contribFrame;  // [nPairs * rowStride] out
+    double*         contribWeight; // [nPairs * rowStride] out: the f64 finalWeight
+    unsigned long long* skipped;   // += pairs out of range or on an empty mixture
+    uint32_t        nMeans, nCovs, nEntries;
+};
+hipError_t launchDensityPosteriors(const PosteriorArgs& a, hipStream_t stream);
+// the same expansion without a scorer: every mixture holds one density (pair.mixOff: the estimator's offsets), its
+// posterior is 1; rowStride is 1, posteriors and logDen are not written
+hipError_t launchExpandSingleDensity(const PosteriorArgs& a, hipStream_t stream);
 // quantized LDS kernel: the never-winning stand-in tile after the segment ring (operands, row constants,
 // PRESEL cluster offsets)
 constexpr uint32_t kI8DummyTileBytes(int ks, bool presel) { return static_cast<uint32_t>(ks) * 1024u + 64u + (presel ? 64u : 0u); }

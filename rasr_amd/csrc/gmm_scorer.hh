@@ -185,6 +185,7 @@ struct PairTables {
     int                    kind = kPairSimd;
     uint32_t               L = 0, nb = 0, isvStride = 0;
     uint32_t               nEntries = 0;  // mixture entries of the shard (rows of the tables below)
+    uint32_t               maxEntries = 0;  // of one mixture: the least row of gmm_density_posteriors_pairs_*
     DeviceBuffer<uint32_t> dMixOff, dCov;
     DeviceBuffer<uint8_t>  dQMean;
     DeviceBuffer<int32_t>  dQConst;
@@ -308,6 +309,9 @@ int waitAsync(gmm_scorer* s);
 // gmm_hostcall.cc: the sparse best-density path (also the Viterbi branch of gmm_estimator_accumulate_*)
 int      checkPairs(const gmm_scorer* s);  // GMM_ERR_UNSUPPORTED: batch types, sharded handles, no pair tables
 PairArgs pairArgsOf(const gmm_scorer* s, const float* frames, uint32_t nFrames, uint32_t frameStride);
+// checkPairs, and GMM_ERR_UNSUPPORTED for every type but diagonal-sum (gmm_density_posteriors_pairs_*, the Baum-Welch
+// branch of gmm_estimator_accumulate_posteriors_*)
+int checkPosteriors(const gmm_scorer* s);
 
 // gmm_group.cc
 int groupScore(gmm_scorer* s, const float* frames, uint32_t nFrames, uint32_t frameStride, float* scores,

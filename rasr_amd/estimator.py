@@ -1,7 +1,8 @@
 """Python handle over the maximum-likelihood accumulation of include/rasr_gmm_estimator.h.
 
 `Estimator` turns aligned (frame, mixture) pairs into the f64 statistics of a mixture set on the GPU
-(AbstractMixtureSetEstimator::accumulate in Viterbi mode), writes them as a RASR estimator file and estimates
+(AbstractMixtureSetEstimator::accumulate in Viterbi mode, or in Baum-Welch mode with the density posteriors of a
+diagonal-sum scorer), writes them as a RASR estimator file and estimates
 the next mixture set; `combine_estimators` adds several such files (the trainer's combine action, host only).
 """
 from __future__ import annotations
@@ -99,6 +100,53 @@ class Estimator:
             self._h, scorer.handle if scorer is not None else None, _ptr(frames), frames.shape[0], frames.shape[1],
             _ptr(pf), _ptr(pm), _ptr(pd), _ptr(pw), n)
         _capi.check(rc, "gmm_estimator_accumulate_host")
+
+    def accumulate_posteriors_device(self, frames, pair_frame, pair_mixture, pair_weight=None, scorer=None,
+                                     weight_threshold=None, stream=None, n_frames=None) -> None:
+        """gmm_estimator_accumulate_posteriors_device (Baum-Welch mode): every pair is spread over all densities of
+        its mixture by the posteriors of `scorer` (a diagonal-sum Scorer; without one every mixture holds one density
+        of posterior 1); a contribution counts iff pair_weight * posterior > weight_threshold (None: the default,
+        DEFAULT_WEIGHT_THRESHOLD).  Tensors as accumulate_device; needs n_pairs * (largest mixture) <= max_pairs."""
+        import torch
+        f = int(frames.shape[0] if n_frames is None else n_frames)
+        n = int(pair_frame.numel())
+        if frames.dtype != torch.float32 or frames.dim() != 2 or frames.stride(1) != 1:
+            raise ValueError("frames must be a float32 [F, >= D] tensor with unit column stride")
+        for name, t in (("pair_frame", pair_frame), ("pair_mixture", pair_mixture)):
+            if t.numel() != n or t.element_size() != 4 or t.dtype.is_floating_point or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous int32 / uint32 tensor of n_pairs entries")
+        if pair_weight is not None and (pair_weight.numel() != n or pair_weight.dtype != torch.float64
+                                        or not pair_weight.is_contiguous()):
+            raise ValueError("pair_weight must be a contiguous float64 tensor of n_pairs entries")
+        if stream is None:
+            stream = torch.cuda.current_stream(frames.device)
+        s = getattr(stream, "cuda_stream", stream)
+        thr = _capi.DEFAULT_WEIGHT_THRESHOLD if weight_threshold is None else float(weight_threshold)
+
+        def p(t):
+            return None if t is None else ctypes.c_void_p(t.data_ptr())
+        rc = self._lib.gmm_estimator_accumulate_posteriors_device(
+            self._h, scorer.handle if scorer is not None else None, p(frames), f, int(frames.stride(0)), p(pair_frame),
+            p(pair_mixture), p(pair_weight), n, thr, ctypes.c_void_p(s) if s else None)
+        _capi.check(rc, "gmm_estimator_accumulate_posteriors_device")
+
+    def accumulate_posteriors_host(self, frames, pair_frame, pair_mixture, pair_weight=None, scorer=None,
+                                   weight_threshold=None) -> None:
+        """gmm_estimator_accumulate_posteriors_host: the same call on numpy arrays, synchronous."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        if frames.ndim != 2:
+            raise ValueError("frames must be [F, >= D]")
+        pf = np.ascontiguousarray(pair_frame, dtype=np.uint32)
+        pm = np.ascontiguousarray(pair_mixture, dtype=np.uint32)
+        pw = None if pair_weight is None else np.ascontiguousarray(pair_weight, dtype=np.float64)
+        n = pf.shape[0]
+        if pf.ndim != 1 or any(a is not None and a.shape != (n,) for a in (pm, pw)):
+            raise ValueError("the pair arrays must be 1-d arrays of one length")
+        thr = _capi.DEFAULT_WEIGHT_THRESHOLD if weight_threshold is None else float(weight_threshold)
+        rc = self._lib.gmm_estimator_accumulate_posteriors_host(
+            self._h, scorer.handle if scorer is not None else None, _ptr(frames), frames.shape[0], frames.shape[1],
+            _ptr(pf), _ptr(pm), _ptr(pw), n, thr)
+        _capi.check(rc, "gmm_estimator_accumulate_posteriors_host")
 
     @property
     def skipped(self) -> int:

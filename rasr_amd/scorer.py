@@ -72,6 +72,9 @@ class Scorer:
         if mixture_range is not None:
             cfg.mixture_begin, cfg.mixture_end = int(mixture_range[0]), int(mixture_range[1])
         self.max_frames = int(max_frames)
+        # the handle's mixtures [begin, end) of the set (mixture_range; (0, 0) is the whole set)
+        self._mixture_range = ((int(cfg.mixture_begin), int(cfg.mixture_end)) if cfg.mixture_end
+                            else (0, int(len(mixture_set.mixture_offsets)) - 1))
         self._desc = mixture_set.desc()
         h = ctypes.c_void_p()
         if devices is None:
@@ -256,6 +259,59 @@ class Scorer:
                                                      ctypes.c_void_p(pair_mixture.data_ptr()), n,
                                                      ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(s) if s else None)
         _capi.check(rc, "gmm_best_density_pairs_device")
+
+    def max_entries(self) -> int:
+        """The largest entry count of the handle's mixtures: the least row_stride of the posterior calls."""
+        off = np.asarray(self.mixture_set.mixture_offsets, dtype=np.int64)
+        b, e = int(self._mixture_range[0]), int(self._mixture_range[1])
+        counts = np.diff(off[b:e + 1])
+        return int(counts.max()) if counts.size else 0
+
+    def density_posteriors_device(self, frames, pair_frame, pair_mixture, row_stride=None, stream=None, n_frames=None):
+        """gmm_density_posteriors_pairs_device (diagonal-sum only): frames torch cuda f32 [F, >=D]; pair_frame /
+        pair_mixture int32 or uint32 cuda tensors of n_pairs.  Returns (posteriors [n_pairs, row_stride] f32,
+        log_denominator [n_pairs] f32) on the frames' device; row_stride defaults to max_entries().  Asynchronous
+        on `stream`."""
+        import torch
+        f = int(frames.shape[0] if n_frames is None else n_frames)
+        if stream is None:
+            stream = torch.cuda.current_stream(frames.device)
+        s = getattr(stream, "cuda_stream", stream)
+        n = int(pair_frame.numel())
+        if frames.dtype != torch.float32 or frames.dim() != 2 or frames.stride(1) != 1:
+            raise ValueError("frames must be a float32 [F, >= D] tensor with unit column stride")
+        for name, t in (("pair_frame", pair_frame), ("pair_mixture", pair_mixture)):
+            if t.numel() != n or t.element_size() != 4 or t.dtype.is_floating_point or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous int32 / uint32 tensor of n_pairs entries")
+        k = self.max_entries() if row_stride is None else int(row_stride)
+        post = torch.empty((n, k), dtype=torch.float32, device=frames.device)
+        logden = torch.empty((n,), dtype=torch.float32, device=frames.device)
+        rc = self._lib.gmm_density_posteriors_pairs_device(
+            self._h, ctypes.c_void_p(frames.data_ptr()), f, int(frames.stride(0)), ctypes.c_void_p(pair_frame.data_ptr()),
+            ctypes.c_void_p(pair_mixture.data_ptr()), n, ctypes.c_void_p(post.data_ptr()), k,
+            ctypes.c_void_p(logden.data_ptr()), ctypes.c_void_p(s) if s else None)
+        _capi.check(rc, "gmm_density_posteriors_pairs_device")
+        return post, logden
+
+    def density_posteriors(self, frames: np.ndarray, pair_frame, pair_mixture, row_stride=None):
+        """gmm_density_posteriors_pairs_host: the same call on numpy arrays, synchronous.  Returns (posteriors
+        [n_pairs, row_stride] f32, log_denominator [n_pairs] f32)."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        if frames.ndim != 2:
+            raise ValueError("frames must be [F, >= D]")
+        pf = np.ascontiguousarray(pair_frame, dtype=np.uint32)
+        pm = np.ascontiguousarray(pair_mixture, dtype=np.uint32)
+        if pf.ndim != 1 or pf.shape != pm.shape:
+            raise ValueError("pair_frame and pair_mixture must be 1-d arrays of one length")
+        k = self.max_entries() if row_stride is None else int(row_stride)
+        post = np.empty((pf.shape[0], k), np.float32)
+        logden = np.empty(pf.shape[0], np.float32)
+        rc = self._lib.gmm_density_posteriors_pairs_host(
+            self._h, frames.ctypes.data_as(ctypes.c_void_p), frames.shape[0], frames.shape[1],
+            pf.ctypes.data_as(ctypes.c_void_p), pm.ctypes.data_as(ctypes.c_void_p), pf.shape[0],
+            post.ctypes.data_as(ctypes.c_void_p), k, logden.ctypes.data_as(ctypes.c_void_p))
+        _capi.check(rc, "gmm_density_posteriors_pairs_host")
+        return post, logden
 
     def set_timing(self, enable: bool) -> None:
         _capi.check(self._lib.gmm_scorer_set_timing(self._h, int(bool(enable))), "gmm_scorer_set_timing")

@@ -10,6 +10,13 @@ library's stream in this one process:
   sort_sum_ms     the same call with the densities given: the resolve, sort and sum passes alone
   table_ms        one gmm_score_device call with best densities over the same frames
 Prints one JSON line.  DESIGN.md section 11 records the numbers.
+
+--mode posteriors: the Baum-Welch call instead (gmm_estimator_accumulate_posteriors_device), diagonal-sum scorer, by
+default 8192 pairs, one per frame, so max_pairs = 8192 x 160 contribution slots:
+  accumulate_posteriors_ms   the whole call (posterior kernel with the expansion + 3 sorts + sums over all slots)
+  posterior_kernel_ms        gmm_density_posteriors_pairs_device alone
+  viterbi_accumulate_ms      gmm_estimator_accumulate_device of the same pairs with the same scorer
+and the contribution slots of a call and how many of them pass the default weight threshold.
 """
 import argparse
 import ctypes
@@ -78,12 +85,45 @@ def _clock_mhz(torch):
     return out
 
 
+def posterior_rates(args, torch, timer, ms, frames, pair_frame, pair_mixture):
+    F, K = int(pair_frame.numel()), args.densities
+    lib = _capi.load_library()
+    sc = ra.Scorer(ms, "diagonal-sum", max_frames=F)
+    est = ra.Estimator(ms, max_pairs=F * K)
+    post = torch.empty((F, K), dtype=torch.float32, device=frames.device)
+    logden = torch.empty(F, dtype=torch.float32, device=frames.device)
+
+    def kernel():  # the C call on kept tensors: Scorer.density_posteriors_device allocates its outputs
+        rc = lib.gmm_density_posteriors_pairs_device(
+            sc.handle, ctypes.c_void_p(frames.data_ptr()), F, int(frames.stride(0)),
+            ctypes.c_void_p(pair_frame.data_ptr()), ctypes.c_void_p(pair_mixture.data_ptr()), F,
+            ctypes.c_void_p(post.data_ptr()), K, ctypes.c_void_p(logden.data_ptr()), None)
+        _capi.check(rc, "gmm_density_posteriors_pairs_device")
+    torch.cuda.synchronize()
+    r = {"model": f"{args.mixtures} x {args.densities} densities, D = {args.dim}, pooled", "pairs": F,
+         "calls": args.calls, "clock": _clock_mhz(torch), "device": torch.cuda.get_device_name(0)}
+    r["accumulate_posteriors_ms"] = timer.ms_per_call(
+        lambda: est.accumulate_posteriors_device(frames, pair_frame, pair_mixture, scorer=sc, stream=0), args.calls,
+        args.warmup)
+    r["posterior_kernel_ms"] = timer.ms_per_call(kernel, args.calls, args.warmup)
+    r["viterbi_accumulate_ms"] = timer.ms_per_call(
+        lambda: est.accumulate_device(frames, pair_frame, pair_mixture, scorer=sc, stream=0), args.calls, args.warmup)
+    assert est.skipped == 0
+    torch.cuda.synchronize()
+    r["contribution_slots"] = F * K
+    r["contributions_over_threshold"] = int((post.double() > ra.DEFAULT_WEIGHT_THRESHOLD).sum().item())
+    r["clock_after"] = _clock_mhz(torch)
+    sc.close()
+    return r
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--mixtures", type=int, default=5000)
     p.add_argument("--densities", type=int, default=160)
     p.add_argument("--dim", type=int, default=39)
-    p.add_argument("--frames", type=int, default=32768)
+    p.add_argument("--frames", type=int, default=None, help="default: 32768, 8192 in posteriors mode")
+    p.add_argument("--mode", choices=["viterbi", "posteriors"], default="viterbi")
     p.add_argument("--calls", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
     args = p.parse_args()
@@ -91,12 +131,16 @@ def main():
     dev = torch.device("cuda:0")
     hip = _library_hip()
     timer = EventTimer(hip)
-    F = args.frames
+    F = args.frames or (8192 if args.mode == "posteriors" else 32768)
     ms = ra.synthetic_mixture_set(args.mixtures, args.densities, args.dim, seed=2024)
     frames = torch.from_numpy(ra.synthetic_frames(F, args.dim, seed=7)).to(dev)
     rng = np.random.default_rng(8)
     pair_frame = torch.arange(F, dtype=torch.int32, device=dev)  # one pair per frame
     pair_mixture = torch.from_numpy(rng.integers(0, args.mixtures, size=F).astype(np.int32)).to(dev)
+    if args.mode == "posteriors":
+        print(json.dumps(posterior_rates(args, torch, timer, ms, frames, pair_frame, pair_mixture)))
+        timer.close()
+        return
     est = ra.Estimator(ms, max_pairs=F)
     result = {"model": f"{args.mixtures} x {args.densities} densities, D = {args.dim}, pooled", "pairs": F,
               "calls": args.calls, "clock": _clock_mhz(torch), "device": torch.cuda.get_device_name(0), "types": {}}
