@@ -146,6 +146,10 @@ constexpr uint32_t splitWideFrames(uint32_t ks) {
     return !GMM_SPLIT_WIDE ? 0u : ks <= 4 ? 256u : (GMM_SPLIT_WIDE5 && ks == 5) ? 192u : 0u;
 }
 
+// scoreSplitWide addresses a chunk's tiles by a 32-bit byte offset from the chunk's first tile (raw buffer loads at a
+// scalar offset): tiles of at most 5 K steps (5 KiB) below 2^32 bytes, the tiles prefetched past the chunk included
+constexpr uint32_t kSplitWideChunkTiles = (1u << 22) / 5u - 16u;
+
 constexpr uint32_t kSplitLimbs   = 4;
 constexpr uint32_t kSplitXXLimbs = 3;
 // the frame's ||x'||^2 rides in K as three f16 limbs against these powers of two on the model side

@@ -721,6 +721,32 @@ __global__ __launch_bounds__(PRESEL ? kSplitFramesPerBlock / splitPreselNF(KS) *
 #define GMM_SPLIT_WIDE_SLOTS 1  // running minima per column block (1: the two min3 of a block chained; -1.3 %, profiles/r06/s5)
 #endif
 
+// the tile step's scalar and address work ("the waits of the per-tile step"); 0 restores the
+// earlier form of each, for A/B (each at 0 against all at 1, fp32 with best densities at 32768 frames,
+// profiles/r08/ab_switches.txt; the running tags alone, the other four at 0, time as the parent)
+#ifndef GMM_SPLIT_WIDE_BUFLD
+#define GMM_SPLIT_WIDE_BUFLD 1  // tile loads as raw buffer loads at a scalar offset (0: global loads, a 64-bit VALU add; +1.3 %)
+#endif
+#ifndef GMM_SPLIT_WIDE_RUNTAG
+#define GMM_SPLIT_WIDE_RUNTAG 1  // the four tags as running SGPRs (0: built from the tile number in every step; +7.2 %)
+#endif
+#ifndef GMM_SPLIT_WIDE_MIXPF
+#define GMM_SPLIT_WIDE_MIXPF 1  // mixTileOff read one mixture ahead, running output row offset (0: +0.6 %)
+#endif
+#ifndef GMM_SPLIT_WIDE_COLD
+#define GMM_SPLIT_WIDE_COLD 1  // the emit out of line: the steady state falls through from step to step (0: +1.9 %)
+#endif
+#ifndef GMM_SPLIT_WIDE_TAIL
+#define GMM_SPLIT_WIDE_TAIL 1  // loads and scalar work scheduled into the gaps after the epilogue's VALU (0: +1.8 %)
+#endif
+// the buffer resource of the current mixture's score or best-density row (rowOff: the carried row offset)
+#if GMM_SPLIT_WIDE_MIXPF
+#define GMM_WIDE_ROW_RSRC(ptr) \
+    __builtin_amdgcn_make_buffer_rsrc((ptr) + rowOff, (short)0, static_cast<int>(a.nFrames * 4u), 0x00020000)
+#else
+#define GMM_WIDE_ROW_RSRC(ptr) GMM_SPLIT_ROW_RSRC(a, ptr, m)
+#endif
+
 template <int KS, bool BEST>
 __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint32_t* __restrict__ mixTileOff) {
     constexpr uint32_t FPB = splitWideFrames(KS);  // frames of the workgroup's one wave
@@ -735,12 +761,29 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
     const uint32_t m0 = a.chunkMixOff[chunk], m1 = a.chunkMixOff[chunk + 1];
     const uint32_t T0 = mixTileOff[m0], T1 = mixTileOff[m1];
 
+#if GMM_SPLIT_WIDE_BUFLD
+    // the chunk's tiles as a raw buffer (the PF tiles prefetched past T1 included: the tile array's kTilePad tiles
+    // keep them in the allocation): a tile load is resource + scalar offset (tile - T0) * KS KiB + the lane's
+    // constant 16 lane + 1 KiB * s, no address arithmetic in the vector unit.  The offset is 32 bits: the host keeps
+    // a chunk below kSplitWideChunkTiles tiles (chunkTableFor, gmm_score.cc)
+    const auto     tileRsrc = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<char*>(static_cast<const char*>(a.tileH)) + static_cast<size_t>(T0) * (KS * 1024u), (short)0,
+            static_cast<int>((T1 - T0 + PF) * (KS * 1024u)), 0x00020000);
+    const uint32_t laneOff  = static_cast<uint32_t>(lane) * 16u;
+    const auto     loadTile = [&](uint32_t tt, f16x8(&A)[KS]) __attribute__((always_inline)) {
+        const uint32_t so = (tt - T0) * (KS * 1024u);
+#pragma unroll
+        for (int s = 0; s < KS; ++s)
+            A[s] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(tileRsrc, laneOff + 1024u * s, so, 0));
+    };
+#else
     const f16x8* th       = static_cast<const f16x8*>(a.tileH);
     const auto   loadTile = [&](uint32_t tt, f16x8(&A)[KS]) {
 #pragma unroll
         for (int s = 0; s < KS; ++s)
             A[s] = th[(static_cast<size_t>(tt) * KS + s) * 64 + lane];
     };
+#endif
     // Frames of the column blocks: column c of block 4 h + q is frame frame0 + NH (16 q + c) + h, so that the
     // emit's reduce, which leaves block 4 h + q of half h in lane 16 q + c, ends with the NH consecutive frames
     // frame0 + NH lane + h in every lane: one multi-dword store per output row.  The frame fragments lie
@@ -796,13 +839,25 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
             for (int cb = 0; cb < NF; ++cb)
                 acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[s], B[cb][s], acc[cb], 0, 0, 0);
     };
+#if GMM_SPLIT_WIDE_RUNTAG
+    // the tags (tile in the mixture << 2 | r) of the tile the next epilogue takes, as four running SGPRs: + 4 per
+    // tile, back to r at a mixture's end (opaque: one v_and_or_b32 per value)
+    uint32_t   tag[4] = {0u, 1u, 2u, 3u};
+#endif
     const auto epilogue = [&](const f32x4(&acc)[NF], uint32_t tl) __attribute__((always_inline)) {
+#if GMM_SPLIT_WIDE_RUNTAG
+        (void)tl;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            asm("" : "+s"(tag[r]));
+#else
         uint32_t tag[4];  // opaque SGPRs: one v_and_or_b32 per value
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             tag[r] = (tl << 2) | static_cast<uint32_t>(r);
             asm("" : "+s"(tag[r]));
         }
+#endif
 #pragma unroll
         for (int cb = 0; cb < NF; ++cb) {
             uint32_t v[4];
@@ -816,9 +871,26 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
             best[cb][1] = umin3(best[cb][1], v[2], v[3]);
 #endif
         }
+#if GMM_SPLIT_WIDE_RUNTAG
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            tag[r] += 4u;
+#endif
     };
 
     uint32_t   m = m0, tBeg = T0, tEnd = m0 < m1 ? mixTileOff[m0 + 1] : T0;
+#if GMM_SPLIT_WIDE_MIXPF
+    // the end of mixture m + 1, read one mixture ahead: the scalar load has a mixture's steps to arrive
+    // (mixTileOff[m1] = T1 stands in past the chunk's last mixture, where the value is not used)
+    uint32_t tNxt  = mixTileOff[min(m0 + 2u, m1)];
+    size_t rowOff  = static_cast<size_t>(m0 - a.mixBase) * a.scoreStride;  // of mixture m's output rows
+    const auto nextMixture = [&](uint32_t tNext) __attribute__((always_inline)) {
+        ++m;
+        rowOff += a.scoreStride;
+        tEnd = m < m1 ? tNxt : tNext;
+        tNxt = mixTileOff[min(m + 2u, m1)];
+    };
+#endif
     const auto emit = [&]() __attribute__((always_inline)) {
         uint32_t key[NH], idx[NH];
         float    score[NH];
@@ -834,7 +906,7 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
         finalizeSplit<BEST, NH>(a, key, kmask, eOut, noneScore, score, idx);
         // lane l holds frames frame0 + NH l + h: one store per row (4 halves: buffer_store_dwordx4)
         const uint32_t off = (frame0 + NH * static_cast<uint32_t>(lane)) * 4u;
-        const auto     rs  = GMM_SPLIT_ROW_RSRC(a, a.scores, m);
+        const auto     rs  = GMM_WIDE_ROW_RSRC(a.scores);
         if constexpr (NH == 4)
             __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(score[0]), __float_as_uint(score[1]),
                                                          __float_as_uint(score[2]), __float_as_uint(score[3])},
@@ -844,7 +916,7 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
             for (int h = 0; h < NH; ++h)
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(score[h]), rs, off + 4u * h, 0, GMM_STORE_CPOL);
         if constexpr (BEST) {
-            const auto rb = GMM_SPLIT_ROW_RSRC(a, a.best, m);
+            const auto rb = GMM_WIDE_ROW_RSRC(a.best);
             if constexpr (NH == 4)
                 __builtin_amdgcn_raw_buffer_store_b128(u32x4{idx[0], idx[1], idx[2], idx[3]}, rb, off, 0, GMM_STORE_CPOL);
             else
@@ -854,40 +926,78 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
         }
     };
     const auto advance = [&](uint32_t tNext) __attribute__((always_inline)) {
-        ++m;
         tBeg = tNext;
+#if GMM_SPLIT_WIDE_MIXPF
+        nextMixture(tNext);
+        while (m < m1 && tEnd == tNext) {
+            emit();
+            nextMixture(tNext);
+        }
+#else
+        ++m;
         tEnd = m < m1 ? mixTileOff[m + 1] : tNext;
         while (m < m1 && tEnd == tNext) {
             emit();
             ++m;
             tEnd = m < m1 ? mixTileOff[m + 1] : tNext;
         }
+#endif
     };
     const auto finish = [&](uint32_t tNext) __attribute__((always_inline)) {
+#if GMM_SPLIT_WIDE_COLD
+        if (__builtin_expect(tNext == tEnd, 0)) {
+#else
         if (tNext == tEnd) {
+#endif
             emit();
             resetBest();
             advance(tNext);
+#if GMM_SPLIT_WIDE_RUNTAG
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                tag[r] &= 3u;  // back to r (from the running value: the + 4 stays inside the step on both paths)
+#endif
         }
     };
     constexpr int kIl = GMM_SPLIT_WIDE_IL * NF / 16;  // MFMAs with 2 VALU each: the 6 NF epilogue VALU
+    constexpr int  kIlE  = 3 * NF;  // the gaps the 6 NF epilogue VALU fill
+    constexpr bool kTail = GMM_SPLIT_WIDE_TAIL && kIl >= kIlE && kIlE + KS + 4 <= NF * KS;  // MFMAs left after them
     const auto    step = [&](const f16x8(&A)[KS], f32x4(&cur)[NF], const f32x4(&prev)[NF], uint32_t tPrev)
             __attribute__((always_inline)) {
         chain(A, cur);
         epilogue(prev, tPrev - tBeg);
 #pragma unroll
-        for (int i = 0; i < kIl; ++i) {
+        for (int i = 0; i < (kTail ? kIlE : kIl); ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
             __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);  // VALU
         }
-        __builtin_amdgcn_sched_group_barrier(0x008, NF * KS - kIl, 0);
+        if constexpr (kTail) {
+            // the MFMAs after the epilogue's: the next tile's KS loads one per gap, then the scalar work
+#pragma unroll
+            for (int i = 0; i < KS; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+                __builtin_amdgcn_sched_group_barrier(0x004, 2, 0);  // SALU
+            }
+            __builtin_amdgcn_sched_group_barrier(0x008, NF * KS - kIlE - KS - 4, 0);
+        }
+        else
+            __builtin_amdgcn_sched_group_barrier(0x008, NF * KS - kIl, 0);
     };
 
     resetBest();
     while (m < m1 && tEnd == T0) {  // mixtures without tiles at the start of the chunk
         emit();
+#if GMM_SPLIT_WIDE_MIXPF
+        nextMixture(T0);
+#else
         ++m;
         tEnd = m < m1 ? mixTileOff[m + 1] : T0;
+#endif
     }
     if (T0 < T1) {
         f32x4 acc[2][NF];
@@ -920,6 +1030,8 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
         });
     }
 }
+
+#undef GMM_WIDE_ROW_RSRC
 
 // ---------------------------------------------------------------------------
 // 32-density tiles on v_mfma_f32_32x32x16_f16 (mixtures of <= 512 densities).  Per 16x16x32-equivalent

@@ -123,11 +123,16 @@ int chunkTableFor(gmm_scorer* s, uint32_t nFrameTiles, const ChunkTable** out) {
     if (target > 8)
         target = (target + 7u) / 8u * 8u;
     target                  = std::min<uint32_t>(target, std::max<uint32_t>(1, s->nMix));
-    const uint32_t perChunk = std::max<uint32_t>(1, (s->nTiles + target - 1) / target);
+    uint32_t perChunk = std::max<uint32_t>(1, (s->nTiles + target - 1) / target);
+    // scoreSplitWide: a chunk's tiles within its 32-bit byte offsets (more, shorter chunks where a model is that large)
+    const uint32_t chunkCap = k == Kernel::SplitWide ? kSplitWideChunkTiles : 0xffffffffu;
+    perChunk                = std::min(perChunk, chunkCap / 2u);
     std::vector<uint32_t> off{0};
     uint32_t              acc = 0;
     for (uint32_t m = 0; m < s->nMix; ++m) {
         acc += s->mixTileOff[m + 1] - s->mixTileOff[m];
+        if (acc > chunkCap)  // one mixture of more than half the cap
+            return fail(GMM_ERR_CAPACITY, "a mixture has more tiles than a scoreSplitWide chunk can address");
         if (acc >= perChunk && m + 1 < s->nMix) {
             off.push_back(m + 1);
             acc = 0;
