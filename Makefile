@@ -26,7 +26,8 @@ OBJS      = $(BUILD)/gmm_kernels_i8.o $(BUILD)/gmm_kernels_f32.o $(BUILD)/gmm_ke
             $(BUILD)/gmm_kernels_presel.o $(BUILD)/gmm_presel.o $(BUILD)/gmm_kernels_shard.o $(BUILD)/gmm_hostio.o \
             $(BUILD)/gmm_kernels_direct.o $(BUILD)/gmm_kernels_layout.o $(BUILD)/gmm_shard.o $(BUILD)/gmm_kernels_pairs.o \
             $(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o \
-            $(BUILD)/gmm_kernels_accum.o $(BUILD)/gmm_estimator.o $(BUILD)/gmm_kernels_posterior.o
+            $(BUILD)/gmm_kernels_accum.o $(BUILD)/gmm_estimator.o $(BUILD)/gmm_kernels_posterior.o \
+            $(BUILD)/gmm_kernels_state.o $(BUILD)/gmm_state.o
 # include/rasr_gmm_estimator.h: the units behind it depend on these besides HDRS
 EST_HDRS  = include/rasr_gmm_estimator.h $(SRC)/gmm_estimator.hh
 DRIVER    = $(BUILD)/tests/feature_scorer_driver
@@ -70,6 +71,12 @@ $(BUILD)/gmm_kernels_pairs.o: $(SRC)/gmm_kernels_pairs.hip $(HDRS)
 $(BUILD)/gmm_kernels_posterior.o: $(SRC)/gmm_kernels_posterior.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -c $< -o $@
+
+# state posteriors over a score table (gmm_state_posteriors_*): f64 in a fixed order, every operation an _rn intrinsic.
+# Not one of KERNEL_OBJS
+$(BUILD)/gmm_kernels_state.o: $(SRC)/gmm_kernels_state.hip $(HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # maximum-likelihood accumulation (gmm_estimator_accumulate_*): resolve, inverted indexes (rocPRIM radix sort),
 # ordered f64 sums.  Not one of KERNEL_OBJS: gmm_kernel_id names the scoring kernels the PMC summaries measure
@@ -121,7 +128,7 @@ $(BUILD)/gmm_api.o: $(SRC)/gmm_api.cc $(HDRS) $(BUILD)/kernel_id.h
 	$(HIPCC) $(HOSTFLAGS) -I$(BUILD) -c $< -o $@
 
 # the other units behind include/rasr_gmm.h (gmm_scorer.hh lists them)
-$(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o: $(BUILD)/%.o: $(SRC)/%.cc $(HDRS)
+$(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o $(BUILD)/gmm_state.o: $(BUILD)/%.o: $(SRC)/%.cc $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
 

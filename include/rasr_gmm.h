@@ -268,6 +268,61 @@ int gmm_density_posteriors_pairs_host(gmm_scorer* scorer, const float* frames, u
                                       const uint32_t* pair_frame, const uint32_t* pair_mixture, uint32_t n_pairs,
                                       float* posteriors, uint32_t row_stride, float* log_denominator);
 
+/* State posteriors over a score table: Mm::StatePosteriorFeatureScorer in Viterbi / mixture mode, workMixtureScores +
+ * pruneScores + workPosteriors (StatePosteriorFeatureScorer.cc:81-160) and the list form
+ * posteriorsAndMixtures(IndicesAndWeights&) (cc:258-284): the softmax over the handle's mixtures with priors, a scale
+ * and a pruning threshold, which posterior features (Speech::StatePosteriorFeatureScorerNode), the discriminative
+ * accumulators (Lattice/WeightedAccumulator.hh) and Nn/CtcCriterion.cc read.  All DEVICE pointers, enqueued on `stream`
+ * (a hipStream_t; NULL = default stream), asynchronous.
+ *   scores   [n_mixtures][score_stride] f32, mixture-major as gmm_score_device writes it (any table of that layout;
+ *            n_mixtures is the handle's)
+ *   priors   [n_mixtures] f64 in the -log domain, or NULL: all 0 (the DefaultFilter).  A prior of +inf takes the
+ *            mixture out of the filter (disregard-densities, SingleMixtureFilter) by the arithmetic alone: s = +inf is
+ *            never the minimum, adds exp(-inf) = +0.0 and gets posterior 0
+ *   pruning_threshold >= DBL_MAX: no pruning (the reference's default)
+ * Per frame, over the mixtures m (Mm::Weight is f64, Score f32), every f64 operation rounded once and nothing fused:
+ *     s_m    = prior_m + scale * (f64) score(m)
+ *     min    the strict-compare scan (s_m < min) from DBL_MAX in ascending m -> minimum_score, minimum_index (the
+ *            lowest index on ties; 0xffffffff when no s_m is below DBL_MAX)
+ *     active every m without pruning, else the m with s_m < (pruning_threshold + min)   (strict, f64) -> n_active
+ *     d_m    = min - s_m
+ *     sum    the sum of exp(d_m) over the active m != minimum_index (an entry EQUAL to the minimum at another index
+ *            counts: exp(0) = 1)
+ *     logZ'  = log1p(sum);   p_m = exp(d_m - logZ') for the active m, 0 otherwise;   log_z = logZ' - min
+ * with the device library's f64 exp / log1p.  The reference walks an unordered_map (its summation order is
+ * unspecified); the order here is part of the contract: the mixtures are cut into consecutive pieces of
+ * GMM_STATE_POSTERIOR_CHUNK by mixture index, a piece's terms are added sequentially from 0 in ascending m, the
+ * pieces' sums sequentially from 0 in piece order.  The result therefore does not depend on n_frames, the strides,
+ * the launch geometry or the run (deterministic bit for bit), and s_m, min, minimum_index, the active mask and
+ * n_active, which involve no transcendental, are exact.  A frame without a finite s, or with NaNs, gets what the
+ * arithmetic gives.
+ *   posteriors_f64 [n_mixtures][posterior_stride] p_m, or NULL
+ *   posteriors_f32 [n_mixtures][posterior_stride] (float) p_m (one round-to-nearest narrowing: the Flow node's
+ *                  Sparse::Vector<f32>), or NULL.  May be `scores` itself with posterior_stride == score_stride: the
+ *                  last pass is elementwise, so the table is replaced in place
+ *   log_z, minimum_score, minimum_index, n_active [n_frames] each, or NULL
+ * Columns >= n_frames of every output are never written.
+ * Errors: GMM_ERR_INVALID_ARGUMENT for a NULL handle or NULL scores, every output pointer NULL, a stride below
+ * n_frames, posteriors_f32 == scores with unequal strides (posteriors_f64 == scores always) and a NaN scale;
+ * GMM_ERR_CAPACITY for n_frames above max_frames; GMM_ERR_UNSUPPORTED for a mixture-shard handle (a shard cannot
+ * normalise) and a density-sharded one.  A refused call writes nothing.  The handle's first call allocates the scratch
+ * (per piece and frame of max_frames: the piece's minimum, its index, its sum and its active count); later calls
+ * allocate nothing.  One stream at a time per handle, as for the estimator calls. */
+#define GMM_STATE_POSTERIOR_CHUNK 256 /* mixtures per piece of a frame's sum; part of the numeric contract */
+int gmm_state_posteriors_device(gmm_scorer* scorer, const float* scores, uint32_t n_frames, uint32_t score_stride,
+                                const double* priors, double scale, double pruning_threshold,
+                                float* posteriors_f32, double* posteriors_f64, uint32_t posterior_stride,
+                                double* log_z, double* minimum_score, uint32_t* minimum_index, uint32_t* n_active,
+                                void* stream);
+
+/* The same from HOST frames (row t at frames + t * frame_stride floats) and into HOST outputs: copies the frames in,
+ * scores them with the handle's own gmm_score_device path into a temporary device table, runs the call above on it
+ * and copies the requested outputs out.  Synchronous; allocates per call. */
+int gmm_state_posteriors_host(gmm_scorer* scorer, const float* frames, uint32_t n_frames, uint32_t frame_stride,
+                              const double* priors, double scale, double pruning_threshold,
+                              float* posteriors_f32, double* posteriors_f64, uint32_t posterior_stride,
+                              double* log_z, double* minimum_score, uint32_t* minimum_index, uint32_t* n_active);
+
 /* Page-locked host memory for gmm_score_host's outputs (the buffer a batched caller keeps, e.g.
  * BatchFeatureScorerBase::scores_, BatchFeatureScorer.hh:177-186), so that callers need no HIP
  * headers.  gmm_host_free(NULL) is a no-op. */

@@ -20,6 +20,7 @@ GMM_ERR_DEVICE = -3
 GMM_ERR_OUT_OF_MEMORY = -4
 GMM_ERR_CAPACITY = -5
 GMM_ESTIMATOR_CHUNK = 512  # include/rasr_gmm_estimator.h: part of the accumulation's numeric contract
+STATE_POSTERIOR_CHUNK = 256  # include/rasr_gmm.h GMM_STATE_POSTERIOR_CHUNK: part of the state posteriors' contract
 # GMM_ESTIMATOR_DEFAULT_WEIGHT_THRESHOLD: Core::Type<f32>::epsilon, the Baum-Welch weightThreshold_
 DEFAULT_WEIGHT_THRESHOLD = 2.0 ** -23
 GMM_FLAG_NATIVE_F32 = 1  # gmm_scorer_config.flags
@@ -141,6 +142,14 @@ PROTOTYPES = [
     ("gmm_density_posteriors_pairs_host", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("gmm_state_posteriors_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_double,
+      ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("gmm_state_posteriors_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_double,
+      ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p]),
     ("gmm_host_alloc", ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
     ("gmm_host_free", ctypes.c_int, [ctypes.c_void_p]),
     ("gmm_scorer_quantization", ctypes.c_int, [ctypes.c_void_p, _f32p, _f32p]),

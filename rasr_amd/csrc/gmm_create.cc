@@ -373,6 +373,7 @@ int createScorer(const gmm_mixture_set* ms, gmm_scorer_type type, const gmm_scor
     if (rc != GMM_OK)
         return rc;
     s->mixBase = shard.begin == 0 && shard.end == 0 ? 0 : shard.begin;
+    s->nMixSet = ms->n_mixtures;
     GMM_HIP_CHECK(hipDeviceSynchronize());
     *out = s.release();
     return GMM_OK;

@@ -286,6 +286,29 @@ hipError_t launchDensityPosteriors(const PosteriorArgs& a, hipStream_t stream);
 // the same expansion without a scorer: every mixture holds one density (pair.mixOff: the estimator's offsets), its
 // posterior is 1; rowStride is 1, posteriors and logDen are not written
 hipError_t launchExpandSingleDensity(const PosteriorArgs& a, hipStream_t stream);
+
+// state posteriors over a score table (gmm_state_posteriors_*, gmm_kernels_state.hip): a lane per frame, a workgroup
+// per (256 frames, piece of kStatePieceMixtures mixtures); three passes over the table -- the pieces' minima, their
+// sums, the elementwise write -- each of which combines the pieces' partial results in piece order first
+constexpr uint32_t kStatePieceMixtures = 256;  // GMM_STATE_POSTERIOR_CHUNK
+struct StateArgs {
+    const float*  scores;      // [nMixtures][scoreStride]
+    const double* priors;      // [nMixtures] or NULL: 0
+    double        scale, pruningThreshold;
+    float*        post32;      // [nMixtures][postStride] or NULL; may be scores (postStride == scoreStride)
+    double*       post64;      // [nMixtures][postStride] or NULL
+    double*       logZ;        // [nFrames] each, or NULL
+    double*       minScore;
+    uint32_t*     minIndex;
+    uint32_t*     nActive;
+    // scratch [nPieces][partStride]: the pieces' minima, their mixtures, their sums and their active cells
+    double*       partMin;
+    uint32_t*     partIdx;
+    double*       partSum;
+    uint32_t*     partCount;
+    uint32_t      nFrames, nMixtures, scoreStride, postStride, partStride, nPieces;
+};
+hipError_t launchStatePosteriors(const StateArgs& a, hipStream_t stream);
 // quantized LDS kernel: the never-winning stand-in tile after the segment ring (operands, row constants,
 // PRESEL cluster offsets)
 constexpr uint32_t kI8DummyTileBytes(int ks, bool presel) { return static_cast<uint32_t>(ks) * 1024u + 64u + (presel ? 64u : 0u); }

@@ -1,6 +1,6 @@
 // gmm_scorer.hh -- what the translation units behind include/rasr_gmm.h share: the handle, the owners of its
 // device / pinned memory, events and streams, the error helpers and the functions that cross unit borders
-// (gmm_create.cc, gmm_score.cc, gmm_hostcall.cc, gmm_group.cc, gmm_api.cc).
+// (gmm_create.cc, gmm_score.cc, gmm_hostcall.cc, gmm_group.cc, gmm_state.cc, gmm_api.cc).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -195,6 +195,14 @@ struct PairTables {
     size_t                 stageCap = 0;  // pairs
 };
 
+// gmm_state_posteriors_* (gmm_state.cc), allocated by the handle's first call for max_frames: per (piece of
+// kStatePieceMixtures mixtures, frame) the piece's minimum, its mixture, its sum and its active cells
+struct StateScratch {
+    uint32_t               nPieces = 0, stride = 0;  // rows; row length (max_frames)
+    DeviceBuffer<double>   dPartMin, dPartSum;
+    DeviceBuffer<uint32_t> dPartIdx, dPartCount;
+};
+
 // gmm_score_host_ring: the caller's frames are the rows ring[(first + i) % ringSize], i < nFrames
 struct HostRing {
     const float* frames;
@@ -244,6 +252,7 @@ struct gmm_scorer {
     int               device = 0;
     gmm_scorer_config cfg{};
     uint32_t          D = 0, C = 0, nMix = 0, mixBase = 0;
+    uint32_t          nMixSet = 0;  // mixtures of the whole set (nMix: of the handle's shard)
     uint32_t          nTiles = 0;  // what chunks are cut by: tiles, or entries (direct)
     uint32_t          nFramesPad = 0;
     std::vector<uint32_t>            mixTileOff;  // host copy
@@ -261,6 +270,7 @@ struct gmm_scorer {
             model;
     std::unique_ptr<rasr_gmm::Preselection> presel;
     std::unique_ptr<rasr_gmm::PairTables>   pairs;
+    std::unique_ptr<rasr_gmm::StateScratch> state;  // empty until the first gmm_state_posteriors_* call
     rasr_gmm::HostPipeline                  host;  // empty until the first host call
     // density-sharded handle (gmm_scorer_create_sharded): the parts score, this handle holds the full-table host
     // staging on devices[0]

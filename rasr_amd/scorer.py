@@ -313,6 +313,69 @@ class Scorer:
         _capi.check(rc, "gmm_density_posteriors_pairs_host")
         return post, logden
 
+    def state_posteriors_device(self, scores, priors=None, scale=1.0, pruning_threshold=None, out_f32=None,
+                                out_f64=None, stream=None, n_frames=None):
+        """gmm_state_posteriors_device: scores torch cuda f32 [M, >= F] (row stride = scores.stride(0)), priors None
+        or a float64 cuda tensor of M (-log domain, +inf: the mixture is out), pruning_threshold None: no pruning.
+        out_f32 / out_f64: [M, >= F] tables for the posteriors (one row stride for both); out_f32 may be `scores`
+        itself (in place).  Returns {"log_z", "minimum_score" (float64 [F]), "minimum_index", "n_active" (int32 [F],
+        the uint32 values' bits)} on the scores' device.  Asynchronous on `stream`."""
+        import torch
+        f = int(scores.shape[1] if n_frames is None else n_frames)
+        m = self.n_mixtures()
+        if stream is None:
+            stream = torch.cuda.current_stream(scores.device)
+        s = getattr(stream, "cuda_stream", stream)
+        for name, t, dt in (("scores", scores, torch.float32), ("out_f32", out_f32, torch.float32),
+                            ("out_f64", out_f64, torch.float64)):
+            if t is not None and (t.dtype != dt or t.dim() != 2 or t.shape[0] != m or t.stride(1) != 1):
+                raise ValueError(f"{name} must be a {dt} [{m}, >= F] tensor with unit column stride")
+        if out_f32 is not None and out_f64 is not None and out_f32.stride(0) != out_f64.stride(0):
+            raise ValueError("out_f32 and out_f64 must have the same row stride")
+        if priors is not None and (priors.dtype != torch.float64 or priors.numel() != m or not priors.is_contiguous()):
+            raise ValueError(f"priors must be a contiguous float64 tensor of {m} entries")
+        out = out_f32 if out_f32 is not None else out_f64
+        r = {"log_z": torch.empty(f, dtype=torch.float64, device=scores.device),
+             "minimum_score": torch.empty(f, dtype=torch.float64, device=scores.device),
+             "minimum_index": torch.empty(f, dtype=torch.int32, device=scores.device),
+             "n_active": torch.empty(f, dtype=torch.int32, device=scores.device)}
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        rc = self._lib.gmm_state_posteriors_device(
+            self._h, ptr(scores), f, int(scores.stride(0)), ptr(priors), float(scale),
+            float(np.finfo(np.float64).max if pruning_threshold is None else pruning_threshold), ptr(out_f32),
+            ptr(out_f64), int(out.stride(0)) if out is not None else 0, ptr(r["log_z"]), ptr(r["minimum_score"]),
+            ptr(r["minimum_index"]), ptr(r["n_active"]), ctypes.c_void_p(s) if s else None)
+        _capi.check(rc, "gmm_state_posteriors_device")
+        return r
+
+    def state_posteriors(self, frames: np.ndarray, priors=None, scale=1.0, pruning_threshold=None, dtype=np.float32):
+        """gmm_state_posteriors_host: numpy frames [F, >= D] scored by this handle and turned into state posteriors,
+        synchronous.  Returns {"posteriors" [M, F] of `dtype` (float32 or float64), "log_z", "minimum_score"
+        (float64 [F]), "minimum_index", "n_active" (uint32 [F])}."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        if frames.ndim != 2:
+            raise ValueError("frames must be [F, >= D]")
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("dtype must be float32 or float64")
+        f, m = frames.shape[0], self.n_mixtures()
+        if priors is not None:
+            priors = np.ascontiguousarray(priors, dtype=np.float64)
+            if priors.shape != (m,):
+                raise ValueError(f"priors must hold {m} entries")
+        r = {"posteriors": np.empty((m, f), dtype), "log_z": np.empty(f, np.float64),
+             "minimum_score": np.empty(f, np.float64), "minimum_index": np.empty(f, np.uint32),
+             "n_active": np.empty(f, np.uint32)}
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+        post = ptr(r["posteriors"])
+        rc = self._lib.gmm_state_posteriors_host(
+            self._h, ptr(frames), f, frames.shape[1], ptr(priors), float(scale),
+            float(np.finfo(np.float64).max if pruning_threshold is None else pruning_threshold),
+            post if dtype == np.float32 else None, post if dtype == np.float64 else None, f, ptr(r["log_z"]),
+            ptr(r["minimum_score"]), ptr(r["minimum_index"]), ptr(r["n_active"]))
+        _capi.check(rc, "gmm_state_posteriors_host")
+        return r
+
     def set_timing(self, enable: bool) -> None:
         _capi.check(self._lib.gmm_scorer_set_timing(self._h, int(bool(enable))), "gmm_scorer_set_timing")
 
