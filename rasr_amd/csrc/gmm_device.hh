@@ -20,9 +20,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // re-reads (A/B, profiles/r02/ab/ab_store_nt.txt: -1.4 % fp32, -0.35 % SIMD)
 #define GMM_STORE_CPOL 2
 #endif
-#ifndef GMM_I8_LDS
-#define GMM_I8_LDS 1  // quantized kernel, one covariance: tiles staged through LDS (scoreI8Seg)
-#endif
 
 // ---------------------------------------------------------------------------
 // reference quantizer, device side (mirrors refRoundToInt / refQuantize in gmm_prepare.cc)
@@ -70,20 +67,10 @@ __device__ __forceinline__ void lexMin(float& v, uint32_t& i, float v2, uint32_t
 // load from it is an s_load wherever it sits.  Through a generic pointer, a load after the kernel's own buffer stores
 // (the emit) cannot be proven unclobbered, so the compiler makes it a vector load plus v_readfirstlane and waits
 // s_waitcnt vmcnt(0) for it -- draining every tile load (or LDS-DMA) in flight at each mixture boundary.
-#ifndef GMM_CONST_TABLES
-#define GMM_CONST_TABLES 1
-#endif
-#if GMM_CONST_TABLES
 template <class T>
 __device__ __forceinline__ const __attribute__((address_space(4))) T* constTable(const T* p) {
     return (const __attribute__((address_space(4))) T*)p;
 }
-#else
-template <class T>
-__device__ __forceinline__ const T* constTable(const T* p) {
-    return p;
-}
-#endif
 __device__ __forceinline__ int swapMin32(int x, int y) {
     const auto r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
     return min(static_cast<int>(r[0]), static_cast<int>(r[1]));

@@ -136,14 +136,11 @@ constexpr uint32_t kSplitMainWaves      = kSplitFramesPerBlock / (16 * kSplitNF)
 #ifndef GMM_SPLIT_WIDE
 #define GMM_SPLIT_WIDE 1  // scoreSplitWide for K steps <= 4 without preselection (0: the pair kernel, A/B)
 #endif
-#ifndef GMM_SPLIT_WIDE5
-#define GMM_SPLIT_WIDE5 0  // 192-frame waves at K steps 5 (A/B: no faster than the pair kernel)
-#endif
 // scoreSplitWide (16-row tiles, diagonal-maximum / batch-float without preselection): frames of its one-wave
 // workgroups at ks K steps -- 16 column blocks at K <= 128 (the frame operands fill the 256 AGPRs) -- or 0 where the
 // pair kernel scoreSplit runs
 constexpr uint32_t splitWideFrames(uint32_t ks) {
-    return !GMM_SPLIT_WIDE ? 0u : ks <= 4 ? 256u : (GMM_SPLIT_WIDE5 && ks == 5) ? 192u : 0u;
+    return GMM_SPLIT_WIDE && ks <= 4 ? 256u : 0u;
 }
 
 // scoreSplitWide addresses a chunk's tiles by a 32-bit byte offset from the chunk's first tile (raw buffer loads at a

@@ -898,9 +898,6 @@ __global__ __launch_bounds__(64 * W, (KS == 1 && !PRESEL && GMM_I8_WAVES && W ==
 #ifndef GMM_I8_CLS_LAG
 #define GMM_I8_CLS_LAG 3  // column blocks whose epilogue runs one step late
 #endif
-#ifndef GMM_I8_PRESEL_CPF
-#define GMM_I8_PRESEL_CPF 1  // preselection: the rows' cluster offsets read one tile ahead with the operands
-#endif
 #ifndef GMM_I8_PRESEL_SEG
 // preselection-batch-int: tiles per LDS segment, one workgroup barrier per segment (8: -3.9 % against 4; 16 +4.4 %, the
 // LDS then allows two waves per SIMD; profiles/r06/s6).  A lagged masked epilogue (the score-only step's pipeline, lag
@@ -909,12 +906,6 @@ __global__ __launch_bounds__(64 * W, (KS == 1 && !PRESEL && GMM_I8_WAVES && W ==
 #endif
 #ifndef GMM_I8_PRESEL_WAVES
 #define GMM_I8_PRESEL_WAVES 3  // preselection: waves per SIMD the register allocation must allow
-#endif
-#ifndef GMM_I8_CLS_EARLYB
-#define GMM_I8_CLS_EARLYB 1  // score-only: every prologue load waited for before the loop (see scoreI8Cls)
-#endif
-#ifndef GMM_I8_CLS_DIAG
-#define GMM_I8_CLS_DIAG 0  // timing diagnostics only (wrong results): 1 = no per-mixture emit (the last one aside)
 #endif
 // PRESEL (preselection-batch-int, NF 8): the row constants are biased by 2^31 (the accumulator u = v + 2^31 is
 // compared unsigned) and every candidate is OR-ed with the sign-extended mask byte of its (frame, row cluster), so a
@@ -1055,8 +1046,7 @@ __global__ __launch_bounds__(64 * W, W == 4 ? (PRESEL ? GMM_I8_PRESEL_WAVES : (N
     // loops (it treats the counter as out of order while LDS-DMA is in flight, so no vmcnt(N) clears them), and it puts
     // an s_waitcnt vmcnt(0) before every 2-tile iteration's first MFMA and in every emit -- each draining the DMA queue,
     // i.e. waiting for the segment issued one segment ahead.  Here the wait costs the second segment's landing once.
-    if constexpr (PRESEL || GMM_I8_CLS_EARLYB)
-        __builtin_amdgcn_s_waitcnt(0x0f70);
+    __builtin_amdgcn_s_waitcnt(0x0f70);
 
     // mixture m ends at tile tEnd; its word wCur and the next mixture's end tNext are loaded one mixture ahead
     // (scalar loads whose latency the mixture's steps cover)
@@ -1154,8 +1144,7 @@ __global__ __launch_bounds__(64 * W, W == 4 ? (PRESEL ? GMM_I8_PRESEL_WAVES : (N
     };
     // mixture m ended at tile t: emit it (and the mixtures without tiles that end at t too)
     const auto finish = [&](uint32_t t) {
-        if (!(GMM_I8_CLS_DIAG & 1) || m + 1 == m1)
-            emit(m);
+        emit(m);
         advance();
         while (t == tEnd && m < m1) {
             emitNone(m);
@@ -1165,18 +1154,13 @@ __global__ __launch_bounds__(64 * W, W == 4 ? (PRESEL ? GMM_I8_PRESEL_WAVES : (N
     // the step of one tile: MFMA of block cb beside the epilogue of block cb - LAG (of the previous step for cb <
     // LAG), fenced so the scheduler keeps that pairing.  FIRST: the first tile of a mixture (after boundary()): no
     // pending tail; its candidates set the minima of its first NF - LAG blocks (no reset of those)
-    const auto step = [&](const i32x4& A, const i32x4& P, const i32x4& Cpf, const int8_t* cptr, uint32_t t,
-                          auto firstC, auto prefetch) {
+    const auto step = [&](const i32x4& A, const i32x4& P, const i32x4& C, uint32_t t, auto firstC, auto prefetch) {
         constexpr bool kFirst = decltype(firstC)::value;
-        (void)cptr;
         if constexpr (!PRESEL)
             prefetch();
         if constexpr (PRESEL) {
             // the tile's mask rows: the lane's table entries (LUT indices), then their 8 mask bytes; the rows'
-            // cluster offsets prefetched with the operands (GMM_I8_PRESEL_CPF) or read here
-            i32x4 C = Cpf;
-            if constexpr (!GMM_I8_PRESEL_CPF)
-                C = *reinterpret_cast<const i32x4*>(cptr);
+            // cluster offsets C came one tile ahead with the operands
             // The 64-bit LUT read at a loaded address makes the waitcnt pass drain the LDS-DMA queue (s_waitcnt
             // vmcnt(0)) at every step, since it cannot tell the read from the ring the DMA fills; by then the next
             // segment, issued a segment ahead, has landed.  Two 32-bit reads from split tables avoid the wait but
@@ -1264,16 +1248,15 @@ __global__ __launch_bounds__(64 * W, W == 4 ? (PRESEL ? GMM_I8_PRESEL_WAVES : (N
         const auto rd = [&](int i, i32x4& A, i32x4& P, i32x4& C) {  // (past the segment: read, never used)
             A = *reinterpret_cast<const i32x4*>(pa + i * 1024);
             P = *reinterpret_cast<const i32x4*>(pp + i * 64);
-            if constexpr (PRESEL && GMM_I8_PRESEL_CPF)
+            if constexpr (PRESEL)
                 C = *reinterpret_cast<const i32x4*>(pp + (kSegP - kSegA) + i * 64);
         };
-        const auto cp = [&](int i) { return pp + (kSegP - kSegA) + i * 64; };  // the tile's cluster offsets
         i32x4    A0, P0, C0, A1, P1, C1;  // tile t, and the next one in flight
         uint32_t t = segT0;
         rd(0, A0, P0, C0);
         while (t < segEnd) {
             if (fresh) {  // the first tile of a mixture
-                step(A0, P0, C0, cp(0), t, kFirstTile, [&] { rd(1, A1, P1, C1); });
+                step(A0, P0, C0, t, kFirstTile, [&] { rd(1, A1, P1, C1); });
                 A0 = A1;
                 P0 = P1;
                 C0 = C1;
@@ -1285,13 +1268,13 @@ __global__ __launch_bounds__(64 * W, W == 4 ? (PRESEL ? GMM_I8_PRESEL_WAVES : (N
             const uint32_t mEnd = min(segEnd, tEnd);
             // two tiles per iteration on alternating registers (no copies of the operands in flight)
             for (; t + 2 <= mEnd; t += 2) {
-                step(A0, P0, C0, cp(0), t, kInner, [&] { rd(1, A1, P1, C1); });
-                step(A1, P1, C1, cp(1), t + 1, kInner, [&] { rd(2, A0, P0, C0); });
+                step(A0, P0, C0, t, kInner, [&] { rd(1, A1, P1, C1); });
+                step(A1, P1, C1, t + 1, kInner, [&] { rd(2, A0, P0, C0); });
                 pa += 2048;
                 pp += 128;
             }
             if (t < mEnd) {
-                step(A0, P0, C0, cp(0), t, kInner, [&] { rd(1, A1, P1, C1); });
+                step(A0, P0, C0, t, kInner, [&] { rd(1, A1, P1, C1); });
                 A0 = A1;
                 P0 = P1;
                 C0 = C1;
@@ -1338,7 +1321,6 @@ hipError_t launchPrepareFramesI8(const float* frames, uint32_t nFrames, uint32_t
 
 template <int NF, int KS, bool MULTI, int W = 4>
 static void launchI8T(const I8Args& a, uint32_t grid, hipStream_t s) {
-#if GMM_I8_LDS
     if constexpr (!MULTI) {
         if (a.presel && a.scoreOnly == 2) {  // preselection-batch-int on the slot layout (3 waves per SIMD: registers)
             if constexpr (KS == 1 && kI8PreselNF == 8) {
@@ -1392,7 +1374,6 @@ static void launchI8T(const I8Args& a, uint32_t grid, hipStream_t s) {
                            a.mixTileOff, a.scores, a.best, nullptr);
         return;
     }
-#endif
     hipLaunchKernelGGL((dev::scoreI8<NF, KS, MULTI>), dim3(grid), dim3(256), 0, s, a);
 }
 
@@ -1400,10 +1381,10 @@ hipError_t launchScoreI8(const I8Args& a, uint32_t kSteps, bool multiCov, hipStr
     const uint32_t grid = 8u * ((a.nChunks + 7u) / 8u) * a.nFrameTiles;
     if (grid == 0)
         return hipSuccess;
-    if (a.presel && (multiCov || !GMM_I8_LDS || a.nClusters == 0 || a.nClusters > 256 || !a.selT || !a.tileClu ||
+    if (a.presel && (multiCov || a.nClusters == 0 || a.nClusters > 256 || !a.selT || !a.tileClu ||
                      (kI8PreselNF == 8 && !a.selC)))
         return hipErrorInvalidValue;
-    if (a.scoreOnly && (multiCov || kSteps != 1 || !GMM_I8_LDS || !a.mixOddMask))
+    if (a.scoreOnly && (multiCov || kSteps != 1 || !a.mixOddMask))
         return hipErrorInvalidValue;
     if (a.smallTile && a.presel)
         return hipErrorInvalidValue;  // the preselection kernels keep their frame tile

@@ -53,17 +53,8 @@ constexpr int splitPreselNF(int ks) { return GMM_SPLIT_PRESEL_NF == 8 && ks <= 5
 #ifndef GMM_SPLIT_PF
 #define GMM_SPLIT_PF 2  // tile pairs in flight per wave (scoreSplit without preselection; 3: +2.6 % at D = 39, profiles/r04/s18)
 #endif
-#ifndef GMM_SPLIT_DIAG_HOT
-#define GMM_SPLIT_DIAG_HOT 0  // diagnostic (wrong results): every tile load reads the chunk's first two tiles (L1-hot)
-#endif
-#ifndef GMM_SPLIT_DIAG_NOEMIT
-#define GMM_SPLIT_DIAG_NOEMIT 0
-#endif
 #ifndef GMM_SPLIT_SUM_NF
 #define GMM_SPLIT_SUM_NF 4  // diagonal-sum: column blocks of 16 frames per wave (4 or 8)
-#endif
-#ifndef GMM_SPLIT_TAG_EMIT
-#define GMM_SPLIT_TAG_EMIT 0  // 1: a tile's keys carry (tile << 2) only; the slot r is OR-ed in at the mixture's end
 #endif
 
 namespace rasr_gmm {
@@ -383,19 +374,6 @@ template <bool BEST, int NH, bool SELECT>
 __device__ __forceinline__ void emitMixtureSplit(const SplitArgs& a, const uint32_t (&best)[4 * NH][4], uint32_t m,
                                                  uint32_t frame0, int lane, uint32_t kmask, const int (&eOut)[NH],
                                                  float noneScore) {
-#if GMM_SPLIT_DIAG_NOEMIT  // diagnostic (wrong results): the emit's cost, the minima kept live by one XOR chain
-    {
-        uint32_t x = 0;
-#pragma unroll
-        for (int cb = 0; cb < 4 * NH; ++cb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                x ^= best[cb][r];
-        __builtin_amdgcn_raw_buffer_store_b32(x, GMM_SPLIT_ROW_RSRC(a, a.scores, m),
-                                              static_cast<uint32_t>(frame0 + lane) * 4u, 0, GMM_STORE_CPOL);
-        return;
-    }
-#endif
     uint32_t key[NH], idx[NH];
     float    score[NH];
 #pragma unroll
@@ -404,10 +382,7 @@ __device__ __forceinline__ void emitMixtureSplit(const SplitArgs& a, const uint3
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) {
             const uint32_t(&b)[4] = best[4 * h + cb];
-            if (GMM_SPLIT_TAG_EMIT && kmask)  // slot r's keys carry tile << 2 only: r joins here (all ones stay)
-                k[cb] = min(umin3(b[0], b[1] | 1u, b[2] | 2u), b[3] | 3u);
-            else
-                k[cb] = min(umin3(b[0], b[1], b[2]), b[3]);
+            k[cb]                 = min(umin3(b[0], b[1], b[2]), b[3]);
         }
         reduceKeysSplit<BEST>(k, key[h], grp);
         idx[h] = (((key[h] & kmask & ~3u) | grp) << 2) | (key[h] & 3u);  // tile << 4 | group << 2 | slot
@@ -479,7 +454,7 @@ __global__ __launch_bounds__(PRESEL ? kSplitFramesPerBlock / splitPreselNF(KS) *
     const auto   loadTile = [&](uint32_t tt, f16x8(&A)[KS], uint2& Cw) {
 #pragma unroll
         for (int s = 0; s < KS; ++s)
-            A[s] = th[(static_cast<size_t>(GMM_SPLIT_DIAG_HOT ? T0 + (tt & 1u) : tt) * KS + s) * 64 + lane];
+            A[s] = th[(static_cast<size_t>(tt) * KS + s) * 64 + lane];
         if constexpr (PRESEL)
             Cw = tclu[static_cast<size_t>(tt) * 4 + g];  // rows 4g .. 4g+3: cluster * 64, u16 each
     };
@@ -576,9 +551,8 @@ __global__ __launch_bounds__(PRESEL ? kSplitFramesPerBlock / splitPreselNF(KS) *
         uint32_t tagA[4], tagB[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const uint32_t rr = GMM_SPLIT_TAG_EMIT ? 0u : static_cast<uint32_t>(r);
-            tagA[r] = (tl << 2) | rr;
-            tagB[r] = ((tl + 1u) << 2) | rr;
+            tagA[r] = (tl << 2) | static_cast<uint32_t>(r);
+            tagB[r] = ((tl + 1u) << 2) | static_cast<uint32_t>(r);
             asm("" : "+s"(tagA[r]), "+s"(tagB[r]));
         }
 #pragma unroll
@@ -703,55 +677,34 @@ __global__ __launch_bounds__(PRESEL ? kSplitFramesPerBlock / splitPreselNF(KS) *
 }
 
 // ---------------------------------------------------------------------------
-// scoreSplitWide (GMM_SPLIT_WIDE; no preselection): one wave per workgroup holds NF column blocks of 16 frames --
-// 16 (256 frames) at K steps <= 4 (D <= 40), 12 (192 frames) at 5 (D <= 51), whose f16 fragments fill the
-// accumulator file (256 / 240 AGPRs) -- and walks its chunk ONE tile per pipeline step: the tile's NF x KS MFMAs
-// beside the epilogue of the previous tile.  Against scoreSplit's 128-frame waves every tile fragment a wave loads
-// feeds 2x (1.5x) the MFMAs (less L2-to-CU traffic and per-tile address and loop work per MFMA), and the frame tiles
-// of a chunk run at once on one XCD (4 one-wave workgroups per CU), so the chunk streams through its L2 about once.
-// The min3 takes two slots of the same tile (rows 4g + r: the key's tag carries r), two running minima per block.
+// scoreSplitWide (GMM_SPLIT_WIDE; no preselection, K steps <= 4, D <= 40): one wave per workgroup holds 16 column
+// blocks of 16 frames (256 frames), whose f16 fragments fill the accumulator file (up to 256 AGPRs), and walks its
+// chunk ONE tile per pipeline step: the tile's NF x KS MFMAs beside the epilogue of the previous tile.  Against
+// scoreSplit's 128-frame waves every tile fragment a wave loads feeds twice the MFMAs (less L2-to-CU traffic and
+// per-tile address and loop work per MFMA), and the frame tiles of a chunk run at once on one XCD (4 one-wave
+// workgroups per CU), so the chunk streams through its L2 about once.
+// A full MFMA gap has no room for scalar or address work ("the waits of the per-tile step"), so
+// the step keeps it out of the vector unit and out of the gaps the epilogue fills: tile loads are raw buffer loads
+// at a scalar offset, the keys' tags are running SGPRs, the mixture bounds are read one mixture ahead, the emit
+// is out of line, and the loads and scalar work are scheduled under the MFMAs that follow the epilogue's.
+// The variants measured against each of these are scripts/variants/split_wide_step_ab.patch.
 // ---------------------------------------------------------------------------
 #ifndef GMM_SPLIT_WIDE_PF
 #define GMM_SPLIT_WIDE_PF 3  // tiles in flight
 #endif
 #ifndef GMM_SPLIT_WIDE_IL
-#define GMM_SPLIT_WIDE_IL 64  // MFMAs of a step interleaved 1 : 2 with the epilogue VALU (at 16 blocks; 64 with one slot: -0.5 %, profiles/r06/s5)
+#define GMM_SPLIT_WIDE_IL 64  // MFMAs of a step interleaved 1 : 2 with the epilogue VALU (-0.5 % against 48, profiles/r06/s5)
 #endif
-#ifndef GMM_SPLIT_WIDE_SLOTS
-#define GMM_SPLIT_WIDE_SLOTS 1  // running minima per column block (1: the two min3 of a block chained; -1.3 %, profiles/r06/s5)
-#endif
-
-// the tile step's scalar and address work ("the waits of the per-tile step"); 0 restores the
-// earlier form of each, for A/B (each at 0 against all at 1, fp32 with best densities at 32768 frames,
-// profiles/r08/ab_switches.txt; the running tags alone, the other four at 0, time as the parent)
-#ifndef GMM_SPLIT_WIDE_BUFLD
-#define GMM_SPLIT_WIDE_BUFLD 1  // tile loads as raw buffer loads at a scalar offset (0: global loads, a 64-bit VALU add; +1.3 %)
-#endif
-#ifndef GMM_SPLIT_WIDE_RUNTAG
-#define GMM_SPLIT_WIDE_RUNTAG 1  // the four tags as running SGPRs (0: built from the tile number in every step; +7.2 %)
-#endif
-#ifndef GMM_SPLIT_WIDE_MIXPF
-#define GMM_SPLIT_WIDE_MIXPF 1  // mixTileOff read one mixture ahead, running output row offset (0: +0.6 %)
-#endif
-#ifndef GMM_SPLIT_WIDE_COLD
-#define GMM_SPLIT_WIDE_COLD 1  // the emit out of line: the steady state falls through from step to step (0: +1.9 %)
-#endif
-#ifndef GMM_SPLIT_WIDE_TAIL
-#define GMM_SPLIT_WIDE_TAIL 1  // loads and scalar work scheduled into the gaps after the epilogue's VALU (0: +1.8 %)
-#endif
-// the buffer resource of the current mixture's score or best-density row (rowOff: the carried row offset)
-#if GMM_SPLIT_WIDE_MIXPF
+// the buffer resource of the current mixture's score or best-density row, at the carried row offset rowOff (frames >=
+// nFrames fall outside num_records, as GMM_SPLIT_ROW_RSRC's)
 #define GMM_WIDE_ROW_RSRC(ptr) \
     __builtin_amdgcn_make_buffer_rsrc((ptr) + rowOff, (short)0, static_cast<int>(a.nFrames * 4u), 0x00020000)
-#else
-#define GMM_WIDE_ROW_RSRC(ptr) GMM_SPLIT_ROW_RSRC(a, ptr, m)
-#endif
 
 template <int KS, bool BEST>
 __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint32_t* __restrict__ mixTileOff) {
     constexpr uint32_t FPB = splitWideFrames(KS);  // frames of the workgroup's one wave
     constexpr int      NF = FPB / 16, NH = NF / 4, PF = GMM_SPLIT_WIDE_PF, U = PF % 2 == 0 ? PF : 2 * PF;
-    static_assert(FPB != 0 && NF * KS * 4 <= 256, "the frame operands fill at most the accumulator file");
+    static_assert(FPB == 256, "16 column blocks: the frame operands fill the accumulator file, four frames per lane");
     const int      lane = threadIdx.x & 63;
     const uint32_t g    = static_cast<uint32_t>(lane) >> 4;
     uint32_t       chunk, ft;
@@ -761,7 +714,6 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
     const uint32_t m0 = a.chunkMixOff[chunk], m1 = a.chunkMixOff[chunk + 1];
     const uint32_t T0 = mixTileOff[m0], T1 = mixTileOff[m1];
 
-#if GMM_SPLIT_WIDE_BUFLD
     // the chunk's tiles as a raw buffer (the PF tiles prefetched past T1 included: the tile array's kTilePad tiles
     // keep them in the allocation): a tile load is resource + scalar offset (tile - T0) * KS KiB + the lane's
     // constant 16 lane + 1 KiB * s, no address arithmetic in the vector unit.  The offset is 32 bits: the host keeps
@@ -776,14 +728,6 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
         for (int s = 0; s < KS; ++s)
             A[s] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(tileRsrc, laneOff + 1024u * s, so, 0));
     };
-#else
-    const f16x8* th       = static_cast<const f16x8*>(a.tileH);
-    const auto   loadTile = [&](uint32_t tt, f16x8(&A)[KS]) {
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-            A[s] = th[(static_cast<size_t>(tt) * KS + s) * 64 + lane];
-    };
-#endif
     // Frames of the column blocks: column c of block 4 h + q is frame frame0 + NH (16 q + c) + h, so that the
     // emit's reduce, which leaves block 4 h + q of half h in lane 16 q + c, ends with the NH consecutive frames
     // frame0 + NH lane + h in every lane: one multi-dword store per output row.  The frame fragments lie
@@ -822,7 +766,9 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
     asm volatile("" : "+v"(vmask));
     const float noneScore = __fmul_rn(a.outScale, a.flavor == 2 ? 0.5f * 3.40282347e+38f : 3.40282347e+38f);
 
-    // slot 0: rows 4g, 4g + 1; slot 1: rows 4g + 2, 4g + 3 (GMM_SPLIT_WIDE_SLOTS 1: one slot, the min3 chained)
+    // one running minimum per column block, best[cb][0], over the lane's four rows 4g + r (the key's tag carries r):
+    // two chained min3 per tile.  best[cb][1] stays all ones and drops out of the emit's min; as a plain best[NF] the
+    // kernels compile to other code (register allocation), so collapsing it takes a new kernel id
     uint32_t   best[NF][2];
     const auto resetBest = [&]() {
 #pragma unroll
@@ -839,47 +785,27 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
             for (int cb = 0; cb < NF; ++cb)
                 acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A[s], B[cb][s], acc[cb], 0, 0, 0);
     };
-#if GMM_SPLIT_WIDE_RUNTAG
     // the tags (tile in the mixture << 2 | r) of the tile the next epilogue takes, as four running SGPRs: + 4 per
     // tile, back to r at a mixture's end (opaque: one v_and_or_b32 per value)
     uint32_t   tag[4] = {0u, 1u, 2u, 3u};
-#endif
-    const auto epilogue = [&](const f32x4(&acc)[NF], uint32_t tl) __attribute__((always_inline)) {
-#if GMM_SPLIT_WIDE_RUNTAG
-        (void)tl;
+    const auto epilogue = [&](const f32x4(&acc)[NF]) __attribute__((always_inline)) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             asm("" : "+s"(tag[r]));
-#else
-        uint32_t tag[4];  // opaque SGPRs: one v_and_or_b32 per value
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            tag[r] = (tl << 2) | static_cast<uint32_t>(r);
-            asm("" : "+s"(tag[r]));
-        }
-#endif
 #pragma unroll
         for (int cb = 0; cb < NF; ++cb) {
             uint32_t v[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 v[r] = BEST ? (__float_as_uint(acc[cb][r]) & vmask) | tag[r] : __float_as_uint(acc[cb][r]);
-#if GMM_SPLIT_WIDE_SLOTS == 1
             best[cb][0] = umin3(umin3(best[cb][0], v[0], v[1]), v[2], v[3]);
-#else
-            best[cb][0] = umin3(best[cb][0], v[0], v[1]);
-            best[cb][1] = umin3(best[cb][1], v[2], v[3]);
-#endif
         }
-#if GMM_SPLIT_WIDE_RUNTAG
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             tag[r] += 4u;
-#endif
     };
 
-    uint32_t   m = m0, tBeg = T0, tEnd = m0 < m1 ? mixTileOff[m0 + 1] : T0;
-#if GMM_SPLIT_WIDE_MIXPF
+    uint32_t   m = m0, tEnd = m0 < m1 ? mixTileOff[m0 + 1] : T0;
     // the end of mixture m + 1, read one mixture ahead: the scalar load has a mixture's steps to arrive
     // (mixTileOff[m1] = T1 stands in past the chunk's last mixture, where the value is not used)
     uint32_t tNxt  = mixTileOff[min(m0 + 2u, m1)];
@@ -890,7 +816,6 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
         tEnd = m < m1 ? tNxt : tNext;
         tNxt = mixTileOff[min(m + 2u, m1)];
     };
-#endif
     const auto emit = [&]() __attribute__((always_inline)) {
         uint32_t key[NH], idx[NH];
         float    score[NH];
@@ -904,68 +829,42 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
             idx[h] = (((key[h] & kmask & ~3u) | grp) << 2) | (key[h] & 3u);  // tile << 4 | group << 2 | slot
         }
         finalizeSplit<BEST, NH>(a, key, kmask, eOut, noneScore, score, idx);
-        // lane l holds frames frame0 + NH l + h: one store per row (4 halves: buffer_store_dwordx4)
+        // lane l holds the four frames frame0 + 4 l + h: one buffer_store_dwordx4 per output row
         const uint32_t off = (frame0 + NH * static_cast<uint32_t>(lane)) * 4u;
-        const auto     rs  = GMM_WIDE_ROW_RSRC(a.scores);
-        if constexpr (NH == 4)
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(score[0]), __float_as_uint(score[1]),
-                                                         __float_as_uint(score[2]), __float_as_uint(score[3])},
-                                                   rs, off, 0, GMM_STORE_CPOL);
-        else
-#pragma unroll
-            for (int h = 0; h < NH; ++h)
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(score[h]), rs, off + 4u * h, 0, GMM_STORE_CPOL);
-        if constexpr (BEST) {
-            const auto rb = GMM_WIDE_ROW_RSRC(a.best);
-            if constexpr (NH == 4)
-                __builtin_amdgcn_raw_buffer_store_b128(u32x4{idx[0], idx[1], idx[2], idx[3]}, rb, off, 0, GMM_STORE_CPOL);
-            else
-#pragma unroll
-                for (int h = 0; h < NH; ++h)
-                    __builtin_amdgcn_raw_buffer_store_b32(idx[h], rb, off + 4u * h, 0, GMM_STORE_CPOL);
-        }
+        __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(score[0]), __float_as_uint(score[1]),
+                                                     __float_as_uint(score[2]), __float_as_uint(score[3])},
+                                               GMM_WIDE_ROW_RSRC(a.scores), off, 0, GMM_STORE_CPOL);
+        if constexpr (BEST)
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{idx[0], idx[1], idx[2], idx[3]}, GMM_WIDE_ROW_RSRC(a.best), off, 0,
+                                                   GMM_STORE_CPOL);
     };
+    // after an emit at tile tNext: the next mixture, and the empty ones that also end there
     const auto advance = [&](uint32_t tNext) __attribute__((always_inline)) {
-        tBeg = tNext;
-#if GMM_SPLIT_WIDE_MIXPF
         nextMixture(tNext);
         while (m < m1 && tEnd == tNext) {
             emit();
             nextMixture(tNext);
         }
-#else
-        ++m;
-        tEnd = m < m1 ? mixTileOff[m + 1] : tNext;
-        while (m < m1 && tEnd == tNext) {
-            emit();
-            ++m;
-            tEnd = m < m1 ? mixTileOff[m + 1] : tNext;
-        }
-#endif
     };
+    // the emit of the mixture that ended at tile tNext, if any: out of line (the expected path falls through from step
+    // to step)
     const auto finish = [&](uint32_t tNext) __attribute__((always_inline)) {
-#if GMM_SPLIT_WIDE_COLD
         if (__builtin_expect(tNext == tEnd, 0)) {
-#else
-        if (tNext == tEnd) {
-#endif
             emit();
             resetBest();
             advance(tNext);
-#if GMM_SPLIT_WIDE_RUNTAG
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 tag[r] &= 3u;  // back to r (from the running value: the + 4 stays inside the step on both paths)
-#endif
         }
     };
-    constexpr int kIl = GMM_SPLIT_WIDE_IL * NF / 16;  // MFMAs with 2 VALU each: the 6 NF epilogue VALU
-    constexpr int  kIlE  = 3 * NF;  // the gaps the 6 NF epilogue VALU fill
-    constexpr bool kTail = GMM_SPLIT_WIDE_TAIL && kIl >= kIlE && kIlE + KS + 4 <= NF * KS;  // MFMAs left after them
-    const auto    step = [&](const f16x8(&A)[KS], f32x4(&cur)[NF], const f32x4(&prev)[NF], uint32_t tPrev)
-            __attribute__((always_inline)) {
+    constexpr int  kIl   = GMM_SPLIT_WIDE_IL * NF / 16;  // MFMAs with 2 VALU each: the 6 NF epilogue VALU
+    constexpr int  kIlE  = 3 * NF;                       // the gaps the 6 NF epilogue VALU fill
+    // K steps 4: the MFMAs left after those gaps take the loads and the scalar work; K steps 1 to 3 leave none
+    constexpr bool kTail = kIl >= kIlE && kIlE + KS + 4 <= NF * KS;
+    const auto    step = [&](const f16x8(&A)[KS], f32x4(&cur)[NF], const f32x4(&prev)[NF]) __attribute__((always_inline)) {
         chain(A, cur);
-        epilogue(prev, tPrev - tBeg);
+        epilogue(prev);
 #pragma unroll
         for (int i = 0; i < (kTail ? kIlE : kIl); ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
@@ -992,12 +891,7 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
     resetBest();
     while (m < m1 && tEnd == T0) {  // mixtures without tiles at the start of the chunk
         emit();
-#if GMM_SPLIT_WIDE_MIXPF
         nextMixture(T0);
-#else
-        ++m;
-        tEnd = m < m1 ? mixTileOff[m + 1] : T0;
-#endif
     }
     if (T0 < T1) {
         f32x4 acc[2][NF];
@@ -1007,7 +901,7 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
         // tile tt = T0 + j with j = 1 + i (mod U): operands R[j % PF], accumulators acc[j % 2]
         const auto sub = [&](auto ic, uint32_t tt) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::value, set = (1 + i) % PF, cur = (1 + i) % 2, prv = i % 2;
-            step(R[set], acc[cur], acc[prv], tt - 1);
+            step(R[set], acc[cur], acc[prv]);
             loadTile(tt + PF, R[set]);
             finish(tt);
         };
@@ -1022,7 +916,7 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
                     sub(ic, tt);
                 }
                 else {  // the last tile's epilogue
-                    epilogue(acc[i % 2], tt - 1 - tBeg);
+                    epilogue(acc[i % 2]);
                     finish(tt);
                     live = false;
                 }

@@ -50,10 +50,6 @@ uint32_t paddedFrames(const KernelPlan& plan, uint32_t maxFrames) {
     // scoreI8Cls workgroups of kI8ClsFramesPerBlock frames: the frame tables hold whole workgroups
     if (plan.kernel == Kernel::I8Cls && plan.framesPerBlock > kFramePadQuantum)
         return roundUp(maxFrames, plan.framesPerBlock);
-    // wide workgroups of 192 frames (K steps 5) read up to 191 rows past the call: room for them in the frame
-    // tables, which are laid out in 512-frame quanta
-    if (plan.kernel == Kernel::SplitWide && kSplitFramesPerBlock % plan.framesPerBlock != 0)
-        return roundUp(maxFrames + plan.framesPerBlock, kFramePadQuantum);
     return roundUp(maxFrames, kFramePadQuantum);
 }
 

@@ -93,15 +93,6 @@ __device__ __forceinline__ uint32_t nnSwz(uint32_t r) {
 // half-tile is restaged at least two phases after its last read in either group, and a staged tile is
 // read one phase after the wait that retires it.
 // ---------------------------------------------------------------------------
-#ifndef NN8_STAGGER
-#define NN8_STAGGER 1  // wave group 1 one barrier behind group 0
-#endif
-#ifndef NN8_EARLY
-#define NN8_EARLY 0  // 1: both halves of tile v+1 still missing are staged in p1 (3 phases before the wait)
-#endif
-#ifndef NN8_TOP_COLS_FIRST
-#define NN8_TOP_COLS_FIRST 1  // the C^T top layer's tile order: columns (classes) of one frame tile first
-#endif
 __global__ __launch_bounds__(512) void nnGemm8p(NnGemmArgs a) {
     constexpr uint32_t T = 256, BK = 64, kOp = T * BK;
     const int          lane = threadIdx.x & 63;
@@ -112,7 +103,7 @@ __global__ __launch_bounds__(512) void nnGemm8p(NnGemmArgs a) {
     // workgroups sharing an XCD take consecutive ids: they sweep the tile rows of one column tile (the
     // activations of one frame tile stay in that XCD's L2); the top layer run as C^T (frames as rows) sweeps
     // the columns of one row tile instead, so that its frame tile's activations are the shared operand again
-    const bool         colsFirst = NN8_TOP_COLS_FIRST && a.swapped;
+    const bool         colsFirst = a.swapped;
     const uint32_t     m0 = (colsFirst ? id / nNT : id % nMT) * T, n0 = (colsFirst ? id % nNT : id / nMT) * T;
     const uint32_t     wr = wave >> 2, wc = wave & 3u;
     const uint32_t     nK = a.Kpad / BK;
@@ -189,7 +180,7 @@ __global__ __launch_bounds__(512) void nnGemm8p(NnGemmArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();
-    if (NN8_STAGGER && wr == 1)
+    if (wr == 1)
         __builtin_amdgcn_s_barrier();  // the stagger
 
     FragA fa;
@@ -200,17 +191,14 @@ __global__ __launch_bounds__(512) void nnGemm8p(NnGemmArgs a) {
         // p1
         readA(buf, 0, fa);
         readB(buf, 0, fb0);
-        if (n1) {
+        if (n1)
             stage(1, 1, v + 1, buf ^ 1u);
-            if (NN8_EARLY)
-                stage(0, 1, v + 1, buf ^ 1u);
-        }
         __builtin_amdgcn_s_barrier();
         quadrant(0, 0, fa, fb0);
         __builtin_amdgcn_s_barrier();
         // p2
         readB(buf, 1, fb1);
-        if (!NN8_EARLY && n1)
+        if (n1)
             stage(0, 1, v + 1, buf ^ 1u);
         __builtin_amdgcn_s_barrier();
         quadrant(0, 1, fa, fb1);
@@ -234,7 +222,7 @@ __global__ __launch_bounds__(512) void nnGemm8p(NnGemmArgs a) {
         quadrant(1, 0, fa, fb0);
         __builtin_amdgcn_s_barrier();
     }
-    if (NN8_STAGGER && wr == 0)
+    if (wr == 0)
         __builtin_amdgcn_s_barrier();  // matches group 1's extra barrier
 
     // epilogue: rows m = m0 + 128 (i >> 2) + 64 wr + 16 (i & 3) + 4 (lane >> 4) + rr,
