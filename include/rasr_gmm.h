@@ -352,6 +352,13 @@ int gmm_prepare_quantized_host(const gmm_mixture_set* mixture_set, gmm_scorer_ty
 int gmm_scorer_launch_info(const gmm_scorer* scorer, uint32_t n_frames, uint32_t* n_launches,
                            const char** main_kernel_name);
 
+/* The K-step count that kernel is dispatched on, read-only: every scoring kernel is a template over it and the
+ * host picks the instantiation from the dimension.  Split-f16 models: K steps of 32 (16-row tiles) or of 16 (32-row
+ * tiles); f32 and quantized models: their K steps of 4 / of 64; GMM_FLAG_REFERENCE_ORDER handles: the 4-dimension
+ * blocks of the row layout.  For the parity table of DESIGN.md (tests/test_k_step_ladder.py), so that a test's
+ * idea of the instantiation cannot drift from the host's choice. */
+int gmm_scorer_k_steps(const gmm_scorer* scorer, uint32_t* k_steps);
+
 /* Instrumentation for bench.py: when enabled, every gmm_score_* call records a
  * pair of HIP events on its stream around the scorer kernel (the dominant
  * launch); gmm_scorer_kernel_time synchronizes on the last event and returns

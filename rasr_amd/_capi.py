@@ -159,6 +159,7 @@ PROTOTYPES = [
       ctypes.c_void_p]),
     ("gmm_scorer_launch_info", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint32, _u32p, ctypes.POINTER(ctypes.c_char_p)]),
+    ("gmm_scorer_k_steps", ctypes.c_int, [ctypes.c_void_p, _u32p]),
     ("gmm_scorer_set_timing", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("gmm_scorer_kernel_time", ctypes.c_int,
      [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), _u32p, ctypes.c_int]),

@@ -383,4 +383,21 @@ int gmm_scorer_launch_info(const gmm_scorer* s, uint32_t nFrames, uint32_t* nLau
     return GMM_OK;
 }
 
+int gmm_scorer_k_steps(const gmm_scorer* s, uint32_t* kSteps) {
+    if (!s || !kSteps)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null scorer or output");
+    s = modelOf(s);  // a sharded handle: per part
+    if (const auto* q = s->quantized())
+        *kSteps = q->kSteps;
+    else if (const auto* m = std::get_if<SplitModel>(&s->model))
+        *kSteps = m->kSteps16;
+    else if (const auto* f = std::get_if<F32Model>(&s->model))
+        *kSteps = f->kSteps;
+    else if (const auto* d = std::get_if<DirectModel>(&s->model))
+        *kSteps = (d->L - 4u) / 4u;  // L = 4 nb + 4 (directBlocks)
+    else
+        return fail(GMM_ERR_UNSUPPORTED, "the handle holds no model");
+    return GMM_OK;
+}
+
 }  // extern "C"

@@ -118,6 +118,13 @@ class Scorer:
                     "gmm_scorer_launch_info")
         return name.value.decode()
 
+    def k_steps(self) -> int:
+        """The K-step count that kernel is dispatched on (gmm_scorer_k_steps): K steps of the split, f32 and
+        quantized models, 4-dimension blocks of a reference-order handle."""
+        k = ctypes.c_uint32()
+        _capi.check(self._lib.gmm_scorer_k_steps(self._h, ctypes.byref(k)), "gmm_scorer_k_steps")
+        return k.value
+
     def density_clustering(self):
         """(cluster_of_entry [entries] u8, cluster_means [clusters][Dp] f32 or u8) of a preselection type."""
         n = ctypes.c_uint32()
