@@ -120,6 +120,18 @@ typedef struct {
 /* cache_archive is read-only ("read-only" of the archive, Core/Application.cc:43, 399-400): a clustering that is not
  * found there is built but not written. */
 #define GMM_FLAG_CACHE_ARCHIVE_READ_ONLY 64u
+/* The float types' 1e-4 contract holds on the matrix-core kernels only for models whose means lie within a bounded
+ * distance of the model centre in units of their deviations: the kernels evaluate ||x'||^2 + ||m'||^2 - 2 x'.m' about
+ * one centre (the mean of all means) in f32, and those terms cancel for a frame near a density far from the centre.
+ * gmm_scorer_create predicts the relative error from the model alone (gmm_float_spread_bound) and, where the
+ * prediction exceeds 1e-4:
+ *   diagonal-maximum, batch-diagonal-maximum-float: builds the handle as if GMM_FLAG_REFERENCE_ORDER were set --
+ *     exact, at the vector ALUs' rate; gmm_scorer_launch_info names scoreDirect;
+ *   diagonal-sum, preselection-batch-float (no reference-order path): GMM_ERR_UNSUPPORTED, gmm_last_error() names
+ *     the predicted bound, the contract and this flag.
+ * With this flag the handle keeps the matrix-core kernel and the caller accepts the predicted bound
+ * (gmm_scorer_spread_bound) in place of 1e-4. */
+#define GMM_FLAG_ACCEPT_SPREAD_BOUND 128u
 
 typedef struct gmm_scorer gmm_scorer;
 
@@ -132,7 +144,10 @@ void gmm_default_config(gmm_scorer_config* cfg);
  * call (src/Mm/FeatureScorerFactory.hh:114-122) for the selected type.
  * SIMD-diagonal-maximum with several covariances quantizes each frame per covariance (SimdFeatureScorer.cc:22-35)
  * into a covariances x max_frames x 64 B table: GMM_ERR_UNSUPPORTED, the size in gmm_last_error(), when that table
- * exceeds three quarters of the device's free memory. */
+ * exceeds three quarters of the device's free memory.
+ * Float types: a model whose predicted relative error on the matrix-core kernels exceeds the 1e-4 contract is built
+ * on the reference-order kernel (diagonal-maximum, batch-diagonal-maximum-float) or refused with GMM_ERR_UNSUPPORTED
+ * (diagonal-sum, preselection-batch-float) unless GMM_FLAG_ACCEPT_SPREAD_BOUND is set; see that flag. */
 int gmm_scorer_create(const gmm_mixture_set* mixture_set, gmm_scorer_type type,
                       const gmm_scorer_config* config, int device, gmm_scorer** out);
 int gmm_scorer_destroy(gmm_scorer* scorer);
@@ -153,7 +168,8 @@ int      gmm_scorer_type_of(const gmm_scorer* scorer);
  *                Float types: the kernel orders candidates by the f32 score with its low 6-8 mantissa bits
  *                replaced by a (tile, row) tag, so two densities whose scores agree within ~2^-16
  *                relative may be reported in either order (the lower index wins exact ties); the score
- *                itself stays within the 1e-4 contract.
+ *                itself stays within the 1e-4 contract (|score - reference| <= 1e-4 max(1, |reference|)), which
+ *                gmm_scorer_create keeps by the model's predicted bound (GMM_FLAG_ACCEPT_SPREAD_BOUND).
  * Replaces per-frame Context construction + calculateScoreAndDensity
  * (SimdFeatureScorer.cc:22-35,135-176) and BatchFeatureScorerBase::fillScoreCache
  * (BatchFeatureScorer.cc:98-105). */
@@ -358,6 +374,25 @@ int gmm_scorer_launch_info(const gmm_scorer* scorer, uint32_t n_frames, uint32_t
  * blocks of the row layout.  For the parity table of DESIGN.md (tests/test_k_step_ladder.py), so that a test's
  * idea of the instantiation cannot drift from the host's choice. */
 int gmm_scorer_k_steps(const gmm_scorer* scorer, uint32_t* k_steps);
+
+/* The spread statistic of a model for a float type, and the relative error predicted from it (host only, no device
+ * needed).  With c the centre (the mean of all means), isv the scorer's inverse deviations (its Gaussian scale in)
+ * and c_e the row constant of mixture entry e (minus twice its scaled log weight plus the log norm of its covariance,
+ * so c_e / 2 is the entry's score at its own mean):
+ *     rho_e^2   = sum_d ((mu_e,d - c_d) isv_d)^2          (the entry's own covariance)
+ *     statistic = max over the entries e of the handle's mixtures of  2^-23 rho_e^2 / max(1, |c_e / 2|)
+ *     predicted = kappa * statistic
+ * kappa is 1.5 x the largest ratio of measured relative error to statistic over the kernel families and a ladder of
+ * model spreads on an MI355X (DESIGN.md section 3 has the table).  `config` (NULL: the defaults) gives the scales,
+ * the mixture shard and the layout flags, as for gmm_scorer_create.  Either output may be NULL.
+ * GMM_ERR_UNSUPPORTED for the quantized types (they have no such expansion), GMM_ERR_INVALID_ARGUMENT for a model
+ * the type does not take. */
+int gmm_float_spread_bound(const gmm_mixture_set* mixture_set, gmm_scorer_type type, const gmm_scorer_config* config,
+                           double* statistic, double* predicted);
+/* The same two numbers of a handle, as computed when it was created -- also of one that was routed to the
+ * reference-order kernel because of them; 0, 0 for a handle created with GMM_FLAG_REFERENCE_ORDER itself.  A
+ * density-sharded handle reports the largest of its parts.  GMM_ERR_UNSUPPORTED for the quantized types. */
+int gmm_scorer_spread_bound(const gmm_scorer* scorer, double* statistic, double* predicted);
 
 /* Instrumentation for bench.py: when enabled, every gmm_score_* call records a
  * pair of HIP events on its stream around the scorer kernel (the dominant

@@ -158,6 +158,12 @@ GpuFeatureScorer::GpuFeatureScorer(const Core::Configuration& c, Core::Ref<const
         cfg.cacheArchive         = paramFile(ac);
         cfg.cacheArchiveReadOnly = paramReadOnly(ac);
     }
+    {
+        // float types on a model whose predicted relative error exceeds 1e-4 (INTEGRATION.md "Wide models")
+        static const Core::ParameterBool paramAcceptSpreadBound(
+                "accept-spread-bound", "keep the matrix-core kernel and accept the predicted error bound", false);
+        cfg.acceptSpreadBound = paramAcceptSpreadBound(c);
+    }
     // the batched scorers take the whole buffer into one launch; buffer-size 1 keeps the unbuffered protocol
     // of SIMD-diagonal-maximum / diagonal-maximum (Gpu::createFeatureScorer)
     const Gpu::MixtureSet ms = convertMixtureSet(*mixtureSet);

@@ -11,12 +11,12 @@ from .estimator import Estimator, combine_estimators
 from .mixture_set import (MixtureSet, estimate_mixture_set, estimator_config, parse_mixture_set, ragged_counts,
                           read_mixture_set, synthetic_frames,
                           synthetic_mixture_set, write_mixture_set)
-from .scorer import Scorer, default_config, pinned_empty, prepare_quantized_host
+from .scorer import Scorer, default_config, float_spread_bound, pinned_empty, prepare_quantized_host
 
 __all__ = [
     "BATCH_DIAGONAL_MAXIMUM_FAST", "BATCH_DIAGONAL_MAXIMUM_FLOAT", "BATCH_DIAGONAL_MAXIMUM_INT", "DIAGONAL_MAXIMUM",
     "SIMD_DIAGONAL_MAXIMUM", "SCORER_TYPES", "LIB_PATH", "GmmError", "load_library", "MixtureSet", "ragged_counts",
     "synthetic_frames", "synthetic_mixture_set", "Scorer", "default_config", "pinned_empty", "prepare_quantized_host",
     "read_mixture_set", "parse_mixture_set", "write_mixture_set", "estimate_mixture_set", "estimator_config",
-    "Estimator", "combine_estimators", "DEFAULT_WEIGHT_THRESHOLD", "STATE_POSTERIOR_CHUNK",
+    "Estimator", "combine_estimators", "DEFAULT_WEIGHT_THRESHOLD", "STATE_POSTERIOR_CHUNK", "float_spread_bound",
 ]

@@ -298,19 +298,40 @@ int buildF32(gmm_scorer* s, const gmm_mixture_set& ms, ShardRange shard, const P
     return setupPairs(s, ms, shard, nullptr);
 }
 
-int buildFloat(gmm_scorer* s, const gmm_mixture_set& ms, ShardRange shard) {
-    const bool     presel = isPreselection(s->type);
-    const uint32_t flags  = s->cfg.flags;
-    PreparedFloat  p;
-    std::string    err = prepareFloat(ms, s->flavor, s->cfg.mixture_weight_scale, s->cfg.gaussian_scale, shard, p,
-                                      (flags & GMM_FLAG_NATIVE_F32) == 0,
-                                      (presel || (flags & GMM_FLAG_SPLIT_TILE16)) ? 16u
+// the float layout of a type and config (host only): what buildFloat uploads and gmm_float_spread_bound measures
+std::string prepareFloatFor(const gmm_mixture_set& ms, gmm_scorer_type type, Flavor flavor, const gmm_scorer_config& cfg,
+                            ShardRange shard, PreparedFloat& p) {
+    const uint32_t flags = cfg.flags;
+    return prepareFloat(ms, flavor, cfg.mixture_weight_scale, cfg.gaussian_scale, shard, p,
+                        (flags & GMM_FLAG_NATIVE_F32) == 0,
+                        (isPreselection(type) || (flags & GMM_FLAG_SPLIT_TILE16)) ? 16u
                                                                                   : ((flags & GMM_FLAG_SPLIT_TILE32) ? 32u : 0u));
+}
+
+int buildFloat(gmm_scorer* s, const gmm_mixture_set& ms, ShardRange shard) {
+    const bool    presel = isPreselection(s->type);
+    PreparedFloat p;
+    std::string   err = prepareFloatFor(ms, s->type, s->flavor, s->cfg, shard, p);
     if (!err.empty())
         return fail(GMM_ERR_INVALID_ARGUMENT, err);
     if (presel && (!p.split || p.splitRows != 16))
         return fail(GMM_ERR_UNSUPPORTED, "preselection-batch-float needs the 16-row split-f16 layout (one "
                                          "covariance, dimension <= 83, <= 1024 densities per mixture)");
+    // the contract's condition (gmm_prepare.hh kSpreadKappa): a model predicted above it leaves the expanded form
+    s->spreadStat      = p.spreadStat;
+    s->spreadPredicted = p.spreadPredicted;
+    if (!(p.spreadPredicted <= kFloatContract) && !(s->cfg.flags & GMM_FLAG_ACCEPT_SPREAD_BOUND)) {
+        if (s->type == GMM_DIAGONAL_MAXIMUM || s->type == GMM_BATCH_DIAGONAL_MAXIMUM_FLOAT)
+            return buildDirect(s, ms, shard);  // exact, at the vector ALUs' rate (dimension <= 126 <= 128)
+        char msg[400];
+        std::snprintf(msg, sizeof(msg),
+                      "predicted relative error %.3g of the float kernels on this model (spread statistic %.3g x kappa "
+                      "%.3g) exceeds the %.0e contract, and %s has no reference-order path: set "
+                      "GMM_FLAG_ACCEPT_SPREAD_BOUND to accept the predicted bound in place of the contract",
+                      p.spreadPredicted, p.spreadStat, kSpreadKappa, kFloatContract,
+                      presel ? "preselection-batch-float" : "diagonal-sum");
+        return fail(GMM_ERR_UNSUPPORTED, msg);
+    }
     return p.split ? buildSplit(s, ms, shard, p) : buildF32(s, ms, shard, p);
 }
 
@@ -406,6 +427,41 @@ int gmm_scorer_create(const gmm_mixture_set* ms, gmm_scorer_type type, const gmm
         s->scoresOnly.reset(twin);
     else  // some row's |2 dot + Q| may leave the class layout's range
         gmm_scorer_destroy(twin);
+    return GMM_OK;
+}
+
+int gmm_float_spread_bound(const gmm_mixture_set* ms, gmm_scorer_type type, const gmm_scorer_config* config,
+                           double* statistic, double* predicted) {
+    if (!ms)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null mixture set");
+    bool         ok     = false;
+    const Flavor flavor = flavorOf(type, &ok);
+    if (!ok || isQuantized(flavor))
+        return fail(GMM_ERR_UNSUPPORTED, "the spread bound applies to the float scorer types");
+    gmm_scorer_config cfg;
+    gmm_default_config(&cfg);
+    if (config)
+        cfg = *config;
+    PreparedFloat     p;
+    const std::string err = prepareFloatFor(*ms, type, flavor, cfg, ShardRange{cfg.mixture_begin, cfg.mixture_end}, p);
+    if (!err.empty())
+        return fail(GMM_ERR_INVALID_ARGUMENT, err);
+    if (statistic)
+        *statistic = p.spreadStat;
+    if (predicted)
+        *predicted = p.spreadPredicted;
+    return GMM_OK;
+}
+
+int gmm_scorer_spread_bound(const gmm_scorer* s, double* statistic, double* predicted) {
+    if (!s)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null scorer");
+    if (isQuantized(s->flavor))
+        return fail(GMM_ERR_UNSUPPORTED, "the spread bound applies to the float scorer types");
+    if (statistic)
+        *statistic = s->spreadStat;
+    if (predicted)
+        *predicted = s->spreadPredicted;
     return GMM_OK;
 }
 

@@ -412,6 +412,9 @@ int gmm_scorer_create_sharded(const gmm_mixture_set* ms, gmm_scorer_type type, c
     s->nMix       = ms->n_mixtures;
     s->plan       = kernelPlanOf(*s);
     s->nFramesPad = paddedFrames(s->plan, cfg.max_frames);
+    for (const DensityPart& p : g->parts)  // gmm_scorer_spread_bound: the largest of the parts
+        if (p.scorer && !(p.scorer->spreadPredicted <= s->spreadPredicted))
+            s->spreadStat = p.scorer->spreadStat, s->spreadPredicted = p.scorer->spreadPredicted;
     s->group.reset(g.release());
     *out = s.release();
     return GMM_OK;

@@ -1001,6 +1001,28 @@ std::string prepareFloat(const gmm_mixture_set& ms, Flavor flavor, float mixture
     for (uint32_t c = 0; c < C; ++c)
         for (uint32_t k = 0; k < D; ++k)
             out.isvDevice[static_cast<size_t>(c) * KS * 4 + k] = out.isv[static_cast<size_t>(c) * D + k];
+
+    // ---- spread statistic (gmm_prepare.hh kSpreadKappa): rho_e^2 as the layout chosen above forms it ----
+    out.spreadStat = 0;
+    for (uint32_t e = ms.mixture_offsets[shard.begin]; e < ms.mixture_offsets[shard.end]; ++e) {
+        const uint32_t dns  = ms.mixture_densities[e];
+        const float*   mean = ms.means + static_cast<size_t>(ms.density_mean[dns]) * D;
+        const float*   iv   = out.isv.data() + static_cast<size_t>(ms.density_covariance[dns]) * D;
+        double         mm   = 0;
+        for (uint32_t k = 0; k < D; ++k) {
+            const double mu = static_cast<double>(mean[k]) - out.centre[k];
+            if (out.splitCov)  // covValues: w mu'^2 in f64
+                mm += static_cast<double>(iv[k]) * iv[k] * mu * mu;
+            else {  // entryValues: the f32 operand m'
+                const float mp = static_cast<float>(mu * iv[k]);
+                mm += static_cast<double>(mp) * mp;
+            }
+        }
+        const double v = std::ldexp(mm, -23) / std::max(1.0, std::fabs(0.5 * rowConstant(e)));
+        if (std::isnan(v) || v > out.spreadStat)  // a NaN stays: such a model is never predicted within the contract
+            out.spreadStat = v;
+    }
+    out.spreadPredicted = kSpreadKappa * out.spreadStat;
     return "";
 }
 

@@ -126,7 +126,21 @@ struct PreparedFloat {
     // several covariances on the split kernels (gmm_prepare.cc, the covariance-free expansion): the frame operand
     // is [y^2, y] about the centre (prepareFramesSplitCov), dimScale has 2 D entries, K = 6 D + 4
     bool                  splitCov     = false;
+    // the spread statistic of the laid-out model and the relative error predicted from it (below)
+    double                spreadStat = 0, spreadPredicted = 0;
 };
+
+// The float contract and its condition.  Every layout above evaluates the expanded form
+// ||x'||^2 + ||m'||^2 - 2 x'.m' about one centre in f32, so a frame near entry e sums terms of size
+// rho_e^2 = ||m'_e||^2 (the covariance-free layout: sum_d w_d mu'_d^2) that cancel; the reference squares
+// (mu - x) isv and has no such terms.  The statistic of a model (PreparedFloat::spreadStat) is
+//     max over the handle's mixture entries e of  2^-23 rho_e^2 / max(1, |c_e / 2|),
+// c_e the entry's row constant (c_e / 2: its score at its own mean), and the kernels' relative error is predicted as
+// kSpreadKappa times it, kSpreadKappa being 1.5 x the largest ratio measured on an MI355X (2.42, scoreSplit32 at
+// spread 3; tests/test_float_spread.py, the table in DESIGN.md section 3), rounded up.  A model predicted above kFloatContract does not get the expanded-form kernels unless the
+// caller accepts the predicted bound (GMM_FLAG_ACCEPT_SPREAD_BOUND; gmm_create.cc buildFloat).
+constexpr double kFloatContract = 1e-4;
+constexpr double kSpreadKappa   = 3.65;
 
 
 struct ShardRange {

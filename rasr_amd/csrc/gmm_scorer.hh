@@ -255,6 +255,9 @@ struct gmm_scorer {
     uint32_t          nMixSet = 0;  // mixtures of the whole set (nMix: of the handle's shard)
     uint32_t          nTiles = 0;  // what chunks are cut by: tiles, or entries (direct)
     uint32_t          nFramesPad = 0;
+    // float types: the model's spread statistic and predicted relative error (gmm_prepare.hh kSpreadKappa), which
+    // decided between the expanded-form kernels and the reference-order one; 0 with GMM_FLAG_REFERENCE_ORDER
+    double            spreadStat = 0, spreadPredicted = 0;
     std::vector<uint32_t>            mixTileOff;  // host copy
     rasr_gmm::DeviceBuffer<uint32_t> dMixTileOff;
     rasr_gmm::DeviceBuffer<float>    dIsv;  // every family's inverse deviations, in its own layout

@@ -153,6 +153,8 @@ bool FeatureScorer::init(const MixtureSet& ms, const Configuration& c, uint32_t 
     cfg.cache_archive         = c.cacheArchive.empty() ? nullptr : c.cacheArchive.c_str();
     if (c.cacheArchiveReadOnly)
         cfg.flags |= GMM_FLAG_CACHE_ARCHIVE_READ_ONLY;
+    if (c.acceptSpreadBound)
+        cfg.flags |= GMM_FLAG_ACCEPT_SPREAD_BOUND;
     const gmm_mixture_set d  = ms.descriptor();
     const int rc = c.shardDevices.size() > 1
                            ? gmm_scorer_create_sharded(&d, t, &cfg, c.shardDevices.data(),

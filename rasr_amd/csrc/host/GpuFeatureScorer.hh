@@ -135,6 +135,10 @@ struct Configuration {
     // "density-clustering"; empty: always built
     std::string cacheArchive;
     bool        cacheArchiveReadOnly = false;
+    // float types: keep the matrix-core kernel on a model whose predicted relative error exceeds the 1e-4 contract
+    // (GMM_FLAG_ACCEPT_SPREAD_BOUND; by default such a model runs the reference-order kernel, or -- diagonal-sum,
+    // preselection-batch-float -- is refused)
+    bool        acceptSpreadBound = false;
 };
 
 // ---------------------------------------------------------------------------

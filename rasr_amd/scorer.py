@@ -38,7 +38,7 @@ class Scorer:
                  select_clusters: int = 32, clustering_iterations: int = 5, backoff_score: float = 40000.0,
                  reference_order: bool = False, devices=None, exchange: str = "auto", full_keys: bool = False,
                  no_score_only_twin: bool = False, cache_archive: str | None = None,
-                 cache_archive_read_only: bool = False):
+                 cache_archive_read_only: bool = False, accept_spread_bound: bool = False):
         self._lib = _capi.load_library()
         self.mixture_set = mixture_set
         self.type = _type_id(scorer_type)
@@ -59,6 +59,8 @@ class Scorer:
             cfg.flags |= _capi.GMM_FLAG_FULL_KEYS
         if no_score_only_twin:  # SIMD: serve calls without best densities from the key layout too
             cfg.flags |= _capi.GMM_FLAG_NO_SCORE_ONLY_TWIN
+        if accept_spread_bound:  # float types: the matrix-core kernel whatever the model's spread (spread_bound())
+            cfg.flags |= _capi.GMM_FLAG_ACCEPT_SPREAD_BOUND
         # density preselection ("density-clustering" parameters, preselection-batch-* types)
         cfg.clusters = int(clusters)
         cfg.select_clusters = int(select_clusters)
@@ -124,6 +126,14 @@ class Scorer:
         k = ctypes.c_uint32()
         _capi.check(self._lib.gmm_scorer_k_steps(self._h, ctypes.byref(k)), "gmm_scorer_k_steps")
         return k.value
+
+    def spread_bound(self) -> tuple[float, float]:
+        """(statistic, predicted relative error) of a float type's model as computed at creation
+        (gmm_scorer_spread_bound): above 1e-4 the handle runs scoreDirect unless accept_spread_bound was set."""
+        st, pr = ctypes.c_double(), ctypes.c_double()
+        _capi.check(self._lib.gmm_scorer_spread_bound(self._h, ctypes.byref(st), ctypes.byref(pr)),
+                    "gmm_scorer_spread_bound")
+        return st.value, pr.value
 
     def density_clustering(self):
         """(cluster_of_entry [entries] u8, cluster_means [clusters][Dp] f32 or u8) of a preselection type."""
@@ -440,6 +450,27 @@ def pinned_empty(shape, dtype=np.float32) -> np.ndarray:
     holder = (ctypes.c_char * max(n, 1)).from_address(ptr.value)
     weakref.finalize(holder, lib.gmm_host_free, ptr.value)
     return np.frombuffer(holder, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
+
+
+def float_spread_bound(ms: MixtureSet, scorer_type="diagonal-maximum", mixture_weight_scale: float = 1.0,
+                       gaussian_scale: float = 1.0, mixture_range: tuple[int, int] | None = None,
+                       native_f32: bool = False, split_tile16: bool = False,
+                       split_tile32: bool = False) -> tuple[float, float]:
+    """(statistic, predicted relative error) of a float type on this model (gmm_float_spread_bound; no GPU needed):
+    what Scorer(...) with the same arguments decides its kernel by."""
+    lib = _capi.load_library()
+    cfg = default_config()
+    cfg.mixture_weight_scale = mixture_weight_scale
+    cfg.gaussian_scale = gaussian_scale
+    cfg.flags |= ((_capi.GMM_FLAG_NATIVE_F32 if native_f32 else 0) | (_capi.GMM_FLAG_SPLIT_TILE16 if split_tile16 else 0) |
+                  (_capi.GMM_FLAG_SPLIT_TILE32 if split_tile32 else 0))
+    if mixture_range is not None:
+        cfg.mixture_begin, cfg.mixture_end = int(mixture_range[0]), int(mixture_range[1])
+    d = ms.desc()
+    st, pr = ctypes.c_double(), ctypes.c_double()
+    _capi.check(lib.gmm_float_spread_bound(ctypes.byref(d), _type_id(scorer_type), ctypes.byref(cfg), ctypes.byref(st),
+                                           ctypes.byref(pr)), "gmm_float_spread_bound")
+    return st.value, pr.value
 
 
 def prepare_quantized_host(ms: MixtureSet, scorer_type="SIMD-diagonal-maximum") -> dict:

@@ -295,6 +295,8 @@ int main(int argc, char** argv) {
     // where the clustering came from on stderr ("clustering: built|written|cached")
     if (const char* ca = std::getenv("RASR_DRIVER_CACHE_ARCHIVE"))
         cfg.cacheArchive = ca;
+    if (const char* ab = std::getenv("RASR_DRIVER_ACCEPT_SPREAD_BOUND"))
+        cfg.acceptSpreadBound = atoi(ab) != 0;
     std::string                             err;
     std::unique_ptr<Mm::Gpu::FeatureScorer> scorer = Mm::Gpu::createFeatureScorer(ms, cfg, &err);
     if (!scorer) {

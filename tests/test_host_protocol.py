@@ -28,7 +28,7 @@ def _write_model(path, ms):
 
 
 def _run(tmp_path, ms, frames, kind, buffer_size, segments, model_file=None, protocol="recognizer", shard_devices=None,
-         cache_archive=None, stderr_out=None):
+         cache_archive=None, stderr_out=None, accept_spread_bound=False):
     mp, fp, op = tmp_path / "m.drvmodel", tmp_path / "f.bin", tmp_path / "o.bin"
     if model_file is None:
         _write_model(mp, ms)
@@ -42,6 +42,8 @@ def _run(tmp_path, ms, frames, kind, buffer_size, segments, model_file=None, pro
         env["RASR_DRIVER_SHARD_DEVICES"] = ",".join(str(d) for d in shard_devices)
     if cache_archive:
         env["RASR_DRIVER_CACHE_ARCHIVE"] = str(cache_archive)
+    if accept_spread_bound:
+        env["RASR_DRIVER_ACCEPT_SPREAD_BOUND"] = "1"
     r = subprocess.run([DRIVER, str(mp), str(fp), str(op), kind, str(buffer_size), str(segments), protocol], check=True,
                        timeout=300, env=env, stderr=subprocess.PIPE, text=True)
     if stderr_out is not None:
@@ -348,7 +350,9 @@ def test_best_density_memoized_across_table_switch(gpu, tmp_path, kind, buffer_s
     but above f32's -- so the single-pair answer (the reference's arithmetic: density 1) and the keyed table's
     differ.  The consumer asks bestDensity(0), then every other emission (past kSparseMax single-pair answers: the
     call's whole keyed table is fetched), then bestDensity(0) again: both answers are the same, and the first frame's
-    is the reference's."""
+    is the reference's.  The two never-best densities at +30 put the model's predicted spread bound above the float
+    contract, so the keyed table is asked for with accept_spread_bound: by default this model
+    runs the reference-order kernel, whose table names density 1 itself."""
     ms = ra.synthetic_mixture_set(40, 4, 39, seed=69, weights="random")
     ms.means[1] = ms.means[0]
     ms.means[2:4] = ms.means[0] + 30.0  # never the best: the tie is between densities 0 and 1 in every frame
@@ -356,13 +360,16 @@ def test_best_density_memoized_across_table_switch(gpu, tmp_path, kind, buffer_s
     ms.mixture_log_weights[:4] = [lw, lw + 5e-5, np.log(0.3), np.log(0.2) - 1e-2]
     frames = ra.synthetic_frames(24, 39, seed=70)
     err = []
-    s, b, _ = _run(tmp_path, ms, frames, kind, buffer_size, 1, protocol="memo", stderr_out=err)
+    s, b, _ = _run(tmp_path, ms, frames, kind, buffer_size, 1, protocol="memo", stderr_out=err, accept_spread_bound=True)
     assert "memo mismatches: 0" in err[0], err[0]
     of = oracle.OracleFloatSum(ms) if kind == "diagonal-sum" else oracle.OracleFloat(ms)
     ref_b = of.score(frames)[1]
     assert (ref_b[0] == 1).all()  # the planted tie: the reference names density 1
     assert b[0, 0] == 1
     # the keyed table (what the fetched table holds) names density 0 for this tie: the memo is what kept the answer
-    sc = ra.Scorer(ms, kind, max_frames=24)
+    sc = ra.Scorer(ms, kind, max_frames=24, accept_spread_bound=True)
     assert (sc.score_host(frames)[1][0] == 0).any()
+    if kind == "diagonal-maximum":  # the default handle of this model: routed, exact, the reference's density
+        routed = ra.Scorer(ms, kind, max_frames=24)
+        assert routed.main_kernel() == "scoreDirect" and (routed.score_host(frames)[1][0] == 1).all()
     assert (b != 0xFFFFFFFF).all()
