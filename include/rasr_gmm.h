@@ -132,6 +132,11 @@ typedef struct {
  * With this flag the handle keeps the matrix-core kernel and the caller accepts the predicted bound
  * (gmm_scorer_spread_bound) in place of 1e-4. */
 #define GMM_FLAG_ACCEPT_SPREAD_BOUND 128u
+/* scoreSplitWide (float types, 16-density tiles, dimension <= 40) runs chunks whose mixtures all have the same tile
+ * count in a form with that count fixed at compile time, where one is compiled (gmm_scorer_chunk_forms); scores and
+ * best densities are the generic form's bit for bit.  This flag keeps the generic form for every chunk (tests, A/B
+ * timing). */
+#define GMM_FLAG_SPLIT_WIDE_GENERIC 256u
 
 typedef struct gmm_scorer gmm_scorer;
 
@@ -367,6 +372,18 @@ int gmm_prepare_quantized_host(const gmm_mixture_set* mixture_set, gmm_scorer_ty
  * of the dominant kernel (for profiling scripts). */
 int gmm_scorer_launch_info(const gmm_scorer* scorer, uint32_t n_frames, uint32_t* n_launches,
                            const char** main_kernel_name);
+
+/* How a call of n_frames cuts the handle's mixtures into chunks and which form of the scorer kernel takes them:
+ * *n_uniform chunks run a form compiled for their mixtures' common tile count (scoreSplitWide, see
+ * GMM_FLAG_SPLIT_WIDE_GENERIC), *n_generic the generic one; every other kernel reports all its chunks as generic.  Each
+ * form present is one launch (gmm_scorer_launch_info counts them once a call of that size has been made).  Builds
+ * the chunk table of that call size if no call has yet.  Either output may be NULL. */
+int gmm_scorer_chunk_forms(gmm_scorer* scorer, uint32_t n_frames, uint32_t* n_uniform, uint32_t* n_generic);
+
+/* Tuning and tests: the number of workgroups a call's chunks x frame tiles aim at (0: the kernel's own choice, the
+ * default), i.e. how many mixtures a chunk holds.  Waits for the device and drops the chunk tables built so far;
+ * results do not depend on it. */
+int gmm_scorer_set_chunk_target(gmm_scorer* scorer, uint32_t target_blocks);
 
 /* The K-step count that kernel is dispatched on, read-only: every scoring kernel is a template over it and the
  * host picks the instantiation from the dimension.  Split-f16 models: K steps of 32 (16-row tiles) or of 16 (32-row

@@ -31,6 +31,7 @@ GMM_FLAG_FULL_KEYS = 16  # batch-int / -fast: (score, density) keys instead of t
 GMM_FLAG_NO_SCORE_ONLY_TWIN = 32  # SIMD: no score-only copy of the model (callers that always want best densities)
 GMM_FLAG_CACHE_ARCHIVE_READ_ONLY = 64  # preselection: read the cached clustering, never write it
 GMM_FLAG_ACCEPT_SPREAD_BOUND = 128  # float types: keep the matrix-core kernel, the predicted bound in place of 1e-4
+GMM_FLAG_SPLIT_WIDE_GENERIC = 256  # scoreSplitWide: the generic form for every chunk, uniform ones too
 FLOAT_CONTRACT = 1e-4  # the float types' relative bound
 GMM_CLUSTERING = {0: "built", 1: "written", 2: "cached"}  # gmm_scorer_clustering_source
 
@@ -161,6 +162,8 @@ PROTOTYPES = [
       ctypes.c_void_p]),
     ("gmm_scorer_launch_info", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint32, _u32p, ctypes.POINTER(ctypes.c_char_p)]),
+    ("gmm_scorer_chunk_forms", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, _u32p, _u32p]),
+    ("gmm_scorer_set_chunk_target", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
     ("gmm_scorer_k_steps", ctypes.c_int, [ctypes.c_void_p, _u32p]),
     ("gmm_float_spread_bound", ctypes.c_int,
      [ctypes.POINTER(MixtureSetDesc), ctypes.c_int, ctypes.POINTER(ScorerConfig), _f64p, _f64p]),

@@ -147,6 +147,20 @@ constexpr uint32_t splitWideFrames(uint32_t ks) {
 // scalar offset): tiles of at most 5 K steps (5 KiB) below 2^32 bytes, the tiles prefetched past the chunk included
 constexpr uint32_t kSplitWideChunkTiles = (1u << 22) / 5u - 16u;
 
+// scoreSplitWide's uniform form (a chunk whose mixtures all have T tiles: the loop body is whole mixtures, no mixture
+// bounds are read or tested in it) is compiled at 4 K steps (dimensions 31 to 40, the headline's 39) for these T:
+// 10 (160 densities, the headline) and 8 (128 densities, what splitting to a power of two ends at).  A body is
+// lcm(6, T) steps of about 1.5 KiB of code, 30 and 24 steps; any other T, and the other K steps, run T = 0
+constexpr uint32_t kSplitWideUniformKSteps = 4;
+using SplitWideUniformT = std::integer_sequence<int, 10, 8>;
+template <int... N>
+constexpr bool splitWideUniformTIn(uint32_t t, std::integer_sequence<int, N...>) {
+    return ((t == uint32_t(N)) || ...);
+}
+constexpr bool splitWideUniformT(uint32_t ks, uint32_t t) {
+    return GMM_SPLIT_WIDE && ks == kSplitWideUniformKSteps && splitWideUniformTIn(t, SplitWideUniformT{});
+}
+
 constexpr uint32_t kSplitLimbs   = 4;
 constexpr uint32_t kSplitXXLimbs = 3;
 // the frame's ||x'||^2 rides in K as three f16 limbs against these powers of two on the model side
@@ -185,6 +199,10 @@ struct SplitArgs {
     uint32_t        nClusters;
     int             presel;
     float           backoff;
+    // scoreSplitWide: the launch's chunks as indices into chunkMixOff's table, nChunks of them (NULL: the table's
+    // chunks 0 .. nChunks - 1), and the tile count every mixture of those chunks has (0: any; splitWideUniformT)
+    const uint32_t* chunkList;
+    uint32_t        uniformT;
 };
 
 hipError_t launchPrepareFramesI8(const float* frames, uint32_t nFrames, uint32_t frameStride, uint32_t nFramesPad,

@@ -1372,9 +1372,9 @@ static void launchI8T(const I8Args& a, uint32_t grid, hipStream_t s) {
         }
         hipLaunchKernelGGL((dev::scoreI8Seg<NF, KS, false, kSeg, false, W>), dim3(grid), dim3(64 * W), 0, s, a,
                            a.mixTileOff, a.scores, a.best, nullptr);
-        return;
     }
-    hipLaunchKernelGGL((dev::scoreI8<NF, KS, MULTI>), dim3(grid), dim3(256), 0, s, a);
+    else  // several covariances (one covariance never gets here: no scoreI8<.., false> is instantiated)
+        hipLaunchKernelGGL((dev::scoreI8<NF, KS, MULTI>), dim3(grid), dim3(256), 0, s, a);
 }
 
 hipError_t launchScoreI8(const I8Args& a, uint32_t kSteps, bool multiCov, hipStream_t stream) {

@@ -36,6 +36,7 @@
 // minimum is a float key whose low tileBits mantissa bits hold the tile number.
 #include "gmm_device.hh"
 
+#include <numeric>
 #include <type_traits>
 #include <utility>
 
@@ -688,6 +689,15 @@ __global__ __launch_bounds__(PRESEL ? kSplitFramesPerBlock / splitPreselNF(KS) *
 // at a scalar offset, the keys' tags are running SGPRs, the mixture bounds are read one mixture ahead, the emit
 // is out of line, and the loads and scalar work are scheduled under the MFMAs that follow the epilogue's.
 // The variants measured against each of these are scripts/variants/split_wide_step_ab.patch.
+//
+// T != 0 (uniform chunks, chunkTableFor in gmm_score.cc): every mixture of the chunk has exactly T tiles, so the
+// mixture bounds fall at compile-time places of a loop body of lcm(2 PF, T) steps -- whole mixtures, and the register
+// sets back at their phase.  In that body the keys' tags are constants ((tile in the mixture) << 2 | r, inline
+// operands of the v_and_or_b32), the per-step test for the mixture's end and its branch are gone, mixTileOff is not
+// read, and the emit is a straight-line block behind the step that takes the mixture's last tile.  The same chain,
+// epilogue and emit in the same order: scores and best densities are those of T = 0 bit for bit.  The last step of a
+// body issues the MFMAs of the tile behind it, so the body runs while a further mixture follows; the chunk's last
+// one to lcm / T mixtures, and every chunk of T = 0, take the generic steps below it.
 // ---------------------------------------------------------------------------
 #ifndef GMM_SPLIT_WIDE_PF
 #define GMM_SPLIT_WIDE_PF 3  // tiles in flight
@@ -700,7 +710,7 @@ __global__ __launch_bounds__(PRESEL ? kSplitFramesPerBlock / splitPreselNF(KS) *
 #define GMM_WIDE_ROW_RSRC(ptr) \
     __builtin_amdgcn_make_buffer_rsrc((ptr) + rowOff, (short)0, static_cast<int>(a.nFrames * 4u), 0x00020000)
 
-template <int KS, bool BEST>
+template <int KS, bool BEST, int T>
 __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint32_t* __restrict__ mixTileOff) {
     constexpr uint32_t FPB = splitWideFrames(KS);  // frames of the workgroup's one wave
     constexpr int      NF = FPB / 16, NH = NF / 4, PF = GMM_SPLIT_WIDE_PF, U = PF % 2 == 0 ? PF : 2 * PF;
@@ -710,6 +720,8 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
     uint32_t       chunk, ft;
     if (!mapBlock(a.nChunks, a.nFrameTiles, chunk, ft))
         return;
+    if (a.chunkList)  // this launch's chunks among the table's (a model of uniform and other chunks)
+        chunk = a.chunkList[chunk];
     const uint32_t frame0 = ft * FPB, fb0 = frame0 / 16u;
     const uint32_t m0 = a.chunkMixOff[chunk], m1 = a.chunkMixOff[chunk + 1];
     const uint32_t T0 = mixTileOff[m0], T1 = mixTileOff[m1];
@@ -766,14 +778,13 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
     asm volatile("" : "+v"(vmask));
     const float noneScore = __fmul_rn(a.outScale, a.flavor == 2 ? 0.5f * 3.40282347e+38f : 3.40282347e+38f);
 
-    // one running minimum per column block, best[cb][0], over the lane's four rows 4g + r (the key's tag carries r):
-    // two chained min3 per tile.  best[cb][1] stays all ones and drops out of the emit's min; as a plain best[NF] the
-    // kernels compile to other code (register allocation), so collapsing it takes a new kernel id
-    uint32_t   best[NF][2];
+    // one running minimum per column block over the lane's four rows 4g + r (the key's tag carries r): two chained
+    // min3 per tile
+    uint32_t   best[NF];
     const auto resetBest = [&]() {
 #pragma unroll
         for (int cb = 0; cb < NF; ++cb)
-            best[cb][0] = best[cb][1] = 0xffffffffu;
+            best[cb] = 0xffffffffu;
     };
     const auto chain = [&](const f16x8(&A)[KS], f32x4(&acc)[NF]) __attribute__((always_inline)) {
 #pragma unroll
@@ -798,11 +809,23 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 v[r] = BEST ? (__float_as_uint(acc[cb][r]) & vmask) | tag[r] : __float_as_uint(acc[cb][r]);
-            best[cb][0] = umin3(umin3(best[cb][0], v[0], v[1]), v[2], v[3]);
+            best[cb] = umin3(umin3(best[cb], v[0], v[1]), v[2], v[3]);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             tag[r] += 4u;
+    };
+    // the same with the tile's place in its mixture known at compile time: the tags are inline constants
+    const auto epilogueAt = [&](auto pos, const f32x4(&acc)[NF]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int cb = 0; cb < NF; ++cb) {
+            uint32_t v[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                v[r] = BEST ? (__float_as_uint(acc[cb][r]) & vmask) | ((static_cast<uint32_t>(decltype(pos)::value) << 2) | r)
+                            : __float_as_uint(acc[cb][r]);
+            best[cb] = umin3(umin3(best[cb], v[0], v[1]), v[2], v[3]);
+        }
     };
 
     uint32_t   m = m0, tEnd = m0 < m1 ? mixTileOff[m0 + 1] : T0;
@@ -824,7 +847,7 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
             uint32_t k[4], grp;
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb)
-                k[cb] = min(best[4 * h + cb][0], best[4 * h + cb][1]);
+                k[cb] = best[4 * h + cb];
             reduceKeysSplit<BEST>(k, key[h], grp);
             idx[h] = (((key[h] & kmask & ~3u) | grp) << 2) | (key[h] & 3u);  // tile << 4 | group << 2 | slot
         }
@@ -862,9 +885,7 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
     constexpr int  kIlE  = 3 * NF;                       // the gaps the 6 NF epilogue VALU fill
     // K steps 4: the MFMAs left after those gaps take the loads and the scalar work; K steps 1 to 3 leave none
     constexpr bool kTail = kIl >= kIlE && kIlE + KS + 4 <= NF * KS;
-    const auto    step = [&](const f16x8(&A)[KS], f32x4(&cur)[NF], const f32x4(&prev)[NF]) __attribute__((always_inline)) {
-        chain(A, cur);
-        epilogue(prev);
+    const auto    stepSchedule = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < (kTail ? kIlE : kIl); ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
@@ -887,6 +908,11 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
         else
             __builtin_amdgcn_sched_group_barrier(0x008, NF * KS - kIl, 0);
     };
+    const auto step = [&](const f16x8(&A)[KS], f32x4(&cur)[NF], const f32x4(&prev)[NF]) __attribute__((always_inline)) {
+        chain(A, cur);
+        epilogue(prev);
+        stepSchedule();
+    };
 
     resetBest();
     while (m < m1 && tEnd == T0) {  // mixtures without tiles at the start of the chunk
@@ -898,6 +924,34 @@ __global__ __launch_bounds__(64, 1) void scoreSplitWide(SplitArgs a, const uint3
         chain(R[0], acc[0]);  // tile T0: nothing to finish beside it
         loadTile(T0 + PF, R[0]);
         uint32_t t = T0 + 1;
+        if constexpr (T != 0) {
+            // the uniform chunk's bodies of L steps = MB mixtures: step k takes tile t + k beside the epilogue of
+            // tile t + k - 1, tile k % T of its mixture (the chunk starts a mixture and t - 1 - T0 stays a multiple of
+            // L), and the mixture ends behind the steps with k % T = T - 1.  Every step and every emit is a scheduling
+            // region of its own, as the generic steps' blocks are
+            constexpr int      L = U / std::gcd(U, T) * T, MB = L / T;
+            const uint32_t     nBody = (T1 - T0 - 1u) / L;
+            for (uint32_t b = 0; b < nBody; ++b, t += L)
+                staticFor<L>([&](auto kc) __attribute__((always_inline)) {
+                    constexpr int k = decltype(kc)::value, i = k % U, set = (1 + i) % PF, cur = (1 + i) % 2, prv = i % 2;
+                    chain(R[set], acc[cur]);
+                    epilogueAt(std::integral_constant<int, k % T>{}, acc[prv]);
+                    stepSchedule();
+                    loadTile(t + k + PF, R[set]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (k % T == T - 1) {
+                        emit();
+                        resetBest();
+                        rowOff += a.scoreStride;
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                });
+            // on to the generic steps at their phase 0: mixture m's first tile is t - 1, its epilogue is pending
+            // and the running tags stand at tile 0 (no generic epilogue has run)
+            m += nBody * MB;
+            tEnd = mixTileOff[m + 1];
+            tNxt = mixTileOff[min(m + 2u, m1)];
+        }
         // tile tt = T0 + j with j = 1 + i (mod U): operands R[j % PF], accumulators acc[j % 2]
         const auto sub = [&](auto ic, uint32_t tt) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::value, set = (1 + i) % PF, cur = (1 + i) % 2, prv = i % 2;
@@ -1734,8 +1788,17 @@ template <int KS>
 static void launchSplitK(const SplitArgs& a, Kernel kernel, uint32_t grid, hipStream_t s) {
     if constexpr (splitWideFrames(KS) != 0) {
         if (kernel == Kernel::SplitWide) {
-            hipLaunchKernelGGL((a.best ? dev::scoreSplitWide<KS, true> : dev::scoreSplitWide<KS, false>), dim3(grid), dim3(64),
-                               0, s, a, a.mixTileOff);
+            // a.uniformT: the tile count of every mixture of the launch's chunks (the host's chunk lists), 0: any
+            bool uniform = false;
+            if constexpr (KS == kSplitWideUniformKSteps)
+                uniform = dispatchInt(a.uniformT, SplitWideUniformT{}, [&](auto tc) {
+                    constexpr int T = decltype(tc)::value;
+                    hipLaunchKernelGGL((a.best ? dev::scoreSplitWide<KS, true, T> : dev::scoreSplitWide<KS, false, T>),
+                                       dim3(grid), dim3(64), 0, s, a, a.mixTileOff);
+                });
+            if (!uniform)
+                hipLaunchKernelGGL((a.best ? dev::scoreSplitWide<KS, true, 0> : dev::scoreSplitWide<KS, false, 0>), dim3(grid),
+                                   dim3(64), 0, s, a, a.mixTileOff);
             return;
         }
     }
@@ -1781,7 +1844,8 @@ hipError_t launchScoreSplit(const SplitArgs& a, Kernel kernel, uint32_t kSteps16
         return hipSuccess;
     if ((a.presel != 0) != (kernel == Kernel::SplitPresel) ||
         (a.presel && (a.nClusters == 0 || a.nClusters > 256 || !a.selT || !a.tileClu)) ||
-        (kernel == Kernel::SplitWide && splitWideFrames(kSteps16) == 0))
+        (kernel == Kernel::SplitWide && splitWideFrames(kSteps16) == 0) ||
+        (a.uniformT != 0 && (kernel != Kernel::SplitWide || !splitWideUniformT(kSteps16, a.uniformT))))
         return hipErrorInvalidValue;  // the mask tables are laid out for 16-row tiles and <= 256 clusters; no wide kernel
     bool ok = false;
     switch (kernel) {

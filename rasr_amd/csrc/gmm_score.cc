@@ -78,6 +78,35 @@ int waitAsync(gmm_scorer* s) {
 
 namespace {
 
+// scoreSplitWide: the chunks of the table `off` by kernel form (ChunkTable::Part), in the order of their tile counts.
+// The mixtures keep their order and their chunks; a model whose chunks all take one form gets one part without a list
+int splitWideParts(const gmm_scorer& s, const std::vector<uint32_t>& off, ChunkTable& ct) {
+    const auto*    model   = std::get_if<SplitModel>(&s.model);
+    const bool     generic = (s.cfg.flags & GMM_FLAG_SPLIT_WIDE_GENERIC) != 0 || !model;
+    std::map<uint32_t, std::vector<uint32_t>> byT;  // uniform tile count (0: none) -> chunks
+    for (uint32_t c = 0; c + 1 < off.size(); ++c) {
+        uint32_t T = generic ? 0u : s.mixTileOff[off[c] + 1] - s.mixTileOff[off[c]];
+        for (uint32_t m = off[c]; T != 0 && m < off[c + 1]; ++m)
+            if (s.mixTileOff[m + 1] - s.mixTileOff[m] != T)
+                T = 0;
+        if (T != 0 && !splitWideUniformT(model->kSteps16, T))
+            T = 0;
+        byT[T].push_back(c);
+    }
+    for (auto& [T, list] : byT) {
+        ChunkTable::Part part;
+        part.uniformT = T;
+        part.nChunks  = static_cast<uint32_t>(list.size());
+        if (byT.size() > 1) {
+            const int rc = upload(part.dList, list);
+            if (rc != GMM_OK)
+                return rc;
+        }
+        ct.parts.push_back(std::move(part));
+    }
+    return GMM_OK;
+}
+
 // Cut the shard's mixtures into chunks of about equal tile count so that
 // chunks x frame-tiles gives enough workgroups to fill 256 CUs several times.
 int chunkTableFor(gmm_scorer* s, uint32_t nFrameTiles, const ChunkTable** out) {
@@ -106,7 +135,8 @@ int chunkTableFor(gmm_scorer* s, uint32_t nFrameTiles, const ChunkTable** out) {
     // frames 0.0695 with 2048 vs 0.0729); large calls keep GMM_TARGET_BLOCKS
     const Kernel   k       = s->plan.kernel;
     const uint32_t kTargetBlocks =
-            kOverride ? kOverride
+            s->chunkTarget ? s->chunkTarget  // gmm_scorer_set_chunk_target
+            : kOverride    ? kOverride
             : isSplitKernel(k) ? std::clamp<uint32_t>(nFrameTiles * 256u, 1024u,
                                              k == Kernel::SplitSum ? uint32_t(GMM_TARGET_BLOCKS)           // 64-frame waves: 8192 (A/B)
                                                                    : uint32_t(GMM_SPLIT_TARGET_BLOCKS))
@@ -139,6 +169,8 @@ int chunkTableFor(gmm_scorer* s, uint32_t nFrameTiles, const ChunkTable** out) {
     ct.nChunks = static_cast<uint32_t>(off.size() - 1);
     int rc     = upload(ct.dMixOff, off);
     if (rc != GMM_OK)
+        return rc;
+    if (k == Kernel::SplitWide && (rc = splitWideParts(*s, off, ct)) != GMM_OK)
         return rc;
     *out = &s->chunks.emplace(nFrameTiles, std::move(ct)).first->second;
     return GMM_OK;
@@ -299,7 +331,17 @@ hipError_t launch(const gmm_scorer& s, const SplitModel& m, const Call& c) {
         a.nClusters = s.presel->clustering.nClusters;
     }
     a.backoff = s.cfg.backoff_score;
-    return launchScoreSplit(a, c.plan.kernel, m.kSteps16, c.stream);
+    if (c.ct->parts.empty())
+        return launchScoreSplit(a, c.plan.kernel, m.kSteps16, c.stream);
+    for (const ChunkTable::Part& part : c.ct->parts) {  // scoreSplitWide: its forms, each over its own chunks
+        a.nChunks   = part.nChunks;
+        a.chunkList = part.dList.get();
+        a.uniformT  = part.uniformT;
+        const hipError_t e = launchScoreSplit(a, c.plan.kernel, m.kSteps16, c.stream);
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t prepareFrames(const gmm_scorer& s, const F32Model& m, const Call& c) {
@@ -375,11 +417,54 @@ int gmm_scorer_launch_info(const gmm_scorer* s, uint32_t nFrames, uint32_t* nLau
     if (!s)
         return fail(GMM_ERR_INVALID_ARGUMENT, "null scorer");
     s = modelOf(s);  // a sharded handle: per part
-    (void)nFrames;
-    if (nLaunches)
-        *nLaunches = s->plan.launches;
+    if (nLaunches) {
+        // a scoreSplitWide model of uniform and other chunks: a scorer launch per kernel form (known once a call
+        // of that many frame tiles has built the chunk table)
+        const auto it = s->chunks.find(planFor(*s, std::max(nFrames, 1u)).nFrameTiles);
+        const size_t parts = it != s->chunks.end() ? it->second.parts.size() : 0;
+        *nLaunches = s->plan.launches + static_cast<uint32_t>(parts > 1 ? parts - 1 : 0);
+    }
     if (name)
         *name = s->plan.name;
+    return GMM_OK;
+}
+
+int gmm_scorer_set_chunk_target(gmm_scorer* s, uint32_t targetBlocks) {
+    if (!s)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null scorer");
+    const int wrc = waitAsync(s);
+    if (wrc != GMM_OK)
+        return wrc;
+    for (gmm_scorer* p : s->group ? partsOf(s) : std::vector<gmm_scorer*>{s}) {
+        GMM_HIP_CHECK(hipSetDevice(p->device));
+        GMM_HIP_CHECK(hipDeviceSynchronize());  // no call in flight reads the tables this drops
+        p->chunkTarget = targetBlocks;
+        p->chunks.clear();
+    }
+    return GMM_OK;
+}
+
+int gmm_scorer_chunk_forms(gmm_scorer* s, uint32_t nFrames, uint32_t* nUniform, uint32_t* nGeneric) {
+    if (!s)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null scorer");
+    uint32_t uniform = 0, generic = 0;
+    for (gmm_scorer* p : s->group ? partsOf(s) : std::vector<gmm_scorer*>{s}) {
+        if (p->nMix == 0)
+            continue;
+        GMM_HIP_CHECK(hipSetDevice(p->device));
+        const ChunkTable* ct = nullptr;
+        const int         rc = chunkTableFor(p, planFor(*p, std::max(nFrames, 1u)).nFrameTiles, &ct);
+        if (rc != GMM_OK)
+            return rc;
+        if (ct->parts.empty())
+            generic += ct->nChunks;
+        for (const ChunkTable::Part& part : ct->parts)
+            (part.uniformT ? uniform : generic) += part.nChunks;
+    }
+    if (nUniform)
+        *nUniform = uniform;
+    if (nGeneric)
+        *nGeneric = generic;
     return GMM_OK;
 }
 

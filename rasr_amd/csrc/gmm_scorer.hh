@@ -125,6 +125,15 @@ struct LaunchPlan {
 struct ChunkTable {
     uint32_t               nChunks = 0;
     DeviceBuffer<uint32_t> dMixOff;
+    // scoreSplitWide: the chunks by the form of the kernel that takes them, one launch each on the call's stream.  A
+    // chunk is uniform when its mixtures all have the same tile count T and the kernel is compiled for T
+    // (splitWideUniformT).  Empty for every other kernel: one launch over the whole table
+    struct Part {
+        uint32_t               uniformT = 0;  // 0: the generic form
+        uint32_t               nChunks  = 0;
+        DeviceBuffer<uint32_t> dList;         // the part's chunks; empty where the part is the whole table
+    };
+    std::vector<Part> parts;
 };
 
 // SIMD-diagonal-maximum, batch-*-int, preselection-batch-int (gmm_kernels_i8.hip)
@@ -263,6 +272,7 @@ struct gmm_scorer {
     rasr_gmm::DeviceBuffer<float>    dIsv;  // every family's inverse deviations, in its own layout
     rasr_gmm::KernelPlan             plan;
     std::map<uint32_t, rasr_gmm::ChunkTable> chunks;  // keyed by frame tiles per call
+    uint32_t          chunkTarget = 0;  // gmm_scorer_set_chunk_target: workgroups a call aims at, 0: the kernel's own
     // kernel timing (gmm_scorer_set_timing)
     bool                                                   timing = false;
     std::vector<std::pair<rasr_gmm::Event, rasr_gmm::Event>> events;

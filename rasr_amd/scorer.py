@@ -38,7 +38,8 @@ class Scorer:
                  select_clusters: int = 32, clustering_iterations: int = 5, backoff_score: float = 40000.0,
                  reference_order: bool = False, devices=None, exchange: str = "auto", full_keys: bool = False,
                  no_score_only_twin: bool = False, cache_archive: str | None = None,
-                 cache_archive_read_only: bool = False, accept_spread_bound: bool = False):
+                 cache_archive_read_only: bool = False, accept_spread_bound: bool = False,
+                 split_wide_generic: bool = False):
         self._lib = _capi.load_library()
         self.mixture_set = mixture_set
         self.type = _type_id(scorer_type)
@@ -61,6 +62,8 @@ class Scorer:
             cfg.flags |= _capi.GMM_FLAG_NO_SCORE_ONLY_TWIN
         if accept_spread_bound:  # float types: the matrix-core kernel whatever the model's spread (spread_bound())
             cfg.flags |= _capi.GMM_FLAG_ACCEPT_SPREAD_BOUND
+        if split_wide_generic:  # scoreSplitWide: the generic form for chunks of equal tile counts too
+            cfg.flags |= _capi.GMM_FLAG_SPLIT_WIDE_GENERIC
         # density preselection ("density-clustering" parameters, preselection-batch-* types)
         cfg.clusters = int(clusters)
         cfg.select_clusters = int(select_clusters)
@@ -119,6 +122,18 @@ class Scorer:
         _capi.check(self._lib.gmm_scorer_launch_info(self._h, 1, ctypes.byref(n), ctypes.byref(name)),
                     "gmm_scorer_launch_info")
         return name.value.decode()
+
+    def chunk_forms(self, n_frames: int = 1) -> tuple[int, int]:
+        """(uniform, generic) chunks of a call of n_frames (gmm_scorer_chunk_forms): how many run the scorer kernel's
+        form compiled for their mixtures' common tile count, and how many the generic one."""
+        u, g = ctypes.c_uint32(), ctypes.c_uint32()
+        _capi.check(self._lib.gmm_scorer_chunk_forms(self._h, int(n_frames), ctypes.byref(u), ctypes.byref(g)),
+                    "gmm_scorer_chunk_forms")
+        return u.value, g.value
+
+    def set_chunk_target(self, target_blocks: int) -> None:
+        """Workgroups a call's chunks x frame tiles aim at (gmm_scorer_set_chunk_target; 0: the default)."""
+        _capi.check(self._lib.gmm_scorer_set_chunk_target(self._h, int(target_blocks)), "gmm_scorer_set_chunk_target")
 
     def k_steps(self) -> int:
         """The K-step count that kernel is dispatched on (gmm_scorer_k_steps): K steps of the split, f32 and
