@@ -27,16 +27,20 @@ OBJS      = $(BUILD)/gmm_kernels_i8.o $(BUILD)/gmm_kernels_f32.o $(BUILD)/gmm_ke
             $(BUILD)/gmm_kernels_direct.o $(BUILD)/gmm_kernels_layout.o $(BUILD)/gmm_shard.o $(BUILD)/gmm_kernels_pairs.o \
             $(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o \
             $(BUILD)/gmm_kernels_accum.o $(BUILD)/gmm_estimator.o $(BUILD)/gmm_kernels_posterior.o \
-            $(BUILD)/gmm_kernels_state.o $(BUILD)/gmm_state.o
+            $(BUILD)/gmm_kernels_state.o $(BUILD)/gmm_state.o \
+            $(BUILD)/gmm_kernels_adapt.o $(BUILD)/gmm_adapt.o $(BUILD)/AffineTransformEstimate.o
 # include/rasr_gmm_estimator.h: the units behind it depend on these besides HDRS
 EST_HDRS  = include/rasr_gmm_estimator.h $(SRC)/gmm_estimator.hh
+# include/rasr_gmm_adaptation.h: the units behind it depend on these besides HDRS
+ADAPT_HDRS = include/rasr_gmm_adaptation.h $(SRC)/gmm_adapt.hh
 DRIVER    = $(BUILD)/tests/feature_scorer_driver
 
 REFSORT   = $(BUILD)/tests/refsort_test
 CLASSLAYOUT = $(BUILD)/tests/class_layout_test
 ESTCOMBINE = $(BUILD)/tests/estimator_combine_test
+AFFINEEST = $(BUILD)/tests/affine_estimate_test
 
-all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) oracle check-integration
+all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) oracle check-integration
 
 $(BUILD)/gmm_kernels_i8.o: $(SRC)/gmm_kernels_i8.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -87,6 +91,20 @@ $(BUILD)/gmm_kernels_accum.o: $(SRC)/gmm_kernels_accum.hip $(EST_HDRS)
 $(BUILD)/gmm_estimator.o: $(SRC)/gmm_estimator.cc $(HDRS) $(EST_HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
+
+# affine feature transform (CMLLR) accumulation per speaker key (gmm_affine_accumulate_*): resolve, one sort by key,
+# ordered f64 sums with a correctly rounded division per G term.  Not one of KERNEL_OBJS
+$(BUILD)/gmm_kernels_adapt.o: $(SRC)/gmm_kernels_adapt.hip $(ADAPT_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/gmm_adapt.o: $(SRC)/gmm_adapt.cc $(HDRS) $(EST_HDRS) $(ADAPT_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
+
+$(BUILD)/AffineTransformEstimate.o: $(SRC)/host/AffineTransformEstimate.cc include/rasr_gmm.h include/rasr_gmm_adaptation.h
+	@mkdir -p $(BUILD)
+	g++ $(HOSTFLAGS) -c $< -o $@
 
 # density-sharded exchange keys (BASELINE config 4)
 $(BUILD)/gmm_kernels_shard.o: $(SRC)/gmm_kernels_shard.hip $(HDRS)
@@ -177,6 +195,11 @@ $(ESTCOMBINE): tests/cpp/estimator_combine_test.cc $(SRC)/host/MixtureSetEstimat
                $(HDRS) $(EST_HDRS)
 	@mkdir -p $(BUILD)/tests
 	g++ $(HOSTFLAGS) $(ESTCOMBINE_FLAGS) -o $@ $< $(SRC)/host/MixtureSetEstimatorFile.cc $(SRC)/host/MixtureSetFile.cc -lz
+
+# host check of gmm_affine_estimate (no GPU, no HIP): the estimate unit alone
+$(AFFINEEST): tests/cpp/affine_estimate_test.cc $(SRC)/host/AffineTransformEstimate.cc include/rasr_gmm.h include/rasr_gmm_adaptation.h
+	@mkdir -p $(BUILD)/tests
+	g++ $(HOSTFLAGS) $(AFFINEEST_FLAGS) -o $@ $< $(SRC)/host/AffineTransformEstimate.cc
 
 $(DRIVER): tests/cpp/feature_scorer_driver.cc $(LIB) $(HDRS)
 	@mkdir -p $(BUILD)/tests

@@ -7,6 +7,7 @@ gfx950 + host-side model preparation); this package only binds it.
 from ._capi import (BATCH_DIAGONAL_MAXIMUM_FAST, BATCH_DIAGONAL_MAXIMUM_FLOAT, BATCH_DIAGONAL_MAXIMUM_INT,
                     DEFAULT_WEIGHT_THRESHOLD, DIAGONAL_MAXIMUM, LIB_PATH, SCORER_TYPES, SIMD_DIAGONAL_MAXIMUM, STATE_POSTERIOR_CHUNK,
                     GmmError, load_library)
+from .adaptation import AffineTransformAccumulator, estimate_affine_transform
 from .estimator import Estimator, combine_estimators
 from .mixture_set import (MixtureSet, estimate_mixture_set, estimator_config, parse_mixture_set, ragged_counts,
                           read_mixture_set, synthetic_frames,
@@ -19,4 +20,5 @@ __all__ = [
     "synthetic_frames", "synthetic_mixture_set", "Scorer", "default_config", "pinned_empty", "prepare_quantized_host",
     "read_mixture_set", "parse_mixture_set", "write_mixture_set", "estimate_mixture_set", "estimator_config",
     "Estimator", "combine_estimators", "DEFAULT_WEIGHT_THRESHOLD", "STATE_POSTERIOR_CHUNK", "float_spread_bound",
+    "AffineTransformAccumulator", "estimate_affine_transform",
 ]

@@ -20,6 +20,7 @@ GMM_ERR_DEVICE = -3
 GMM_ERR_OUT_OF_MEMORY = -4
 GMM_ERR_CAPACITY = -5
 GMM_ESTIMATOR_CHUNK = 512  # include/rasr_gmm_estimator.h: part of the accumulation's numeric contract
+GMM_AFFINE_CHUNK = 512  # include/rasr_gmm_adaptation.h: part of the affine accumulation's numeric contract
 STATE_POSTERIOR_CHUNK = 256  # include/rasr_gmm.h GMM_STATE_POSTERIOR_CHUNK: part of the state posteriors' contract
 # GMM_ESTIMATOR_DEFAULT_WEIGHT_THRESHOLD: Core::Type<f32>::epsilon, the Baum-Welch weightThreshold_
 DEFAULT_WEIGHT_THRESHOLD = 2.0 ** -23
@@ -112,7 +113,8 @@ GMM_HOST_ASYNC = 8
 # gmm_scorer_create_sharded: the per-frame reduce of mixtures split between GPUs
 GMM_EXCHANGE = {"auto": 0, "rccl": 1, "copy": 2}
 
-# (name, restype, argtypes) for every function declared in include/rasr_gmm.h, rasr_gmm_io.h and rasr_gmm_estimator.h
+# (name, restype, argtypes) for every function declared in include/rasr_gmm.h, rasr_gmm_io.h, rasr_gmm_estimator.h
+# and rasr_gmm_adaptation.h
 PROTOTYPES = [
     ("gmm_default_config", None, [ctypes.POINTER(ScorerConfig)]),
     ("gmm_scorer_create", ctypes.c_int,
@@ -233,6 +235,28 @@ PROTOTYPES = [
     ("gmm_estimator_combine", ctypes.c_int,
      [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_void_p,
       ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    # include/rasr_gmm_adaptation.h
+    ("gmm_affine_create", ctypes.c_int,
+     [ctypes.POINTER(MixtureSetDesc), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    ("gmm_affine_destroy", ctypes.c_int, [ctypes.c_void_p]),
+    ("gmm_affine_reset", ctypes.c_int, [ctypes.c_void_p]),
+    ("gmm_affine_accumulate_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("gmm_affine_accumulate_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    ("gmm_affine_skipped", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("gmm_affine_info", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
+    ("gmm_affine_get", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, _f64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("gmm_affine_add", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, _f64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_double]),
+    ("gmm_affine_estimate", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+      ctypes.c_uint32, ctypes.c_double, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     ("gmm_version", ctypes.c_char_p, []),
     ("gmm_kernel_id", ctypes.c_char_p, []),
 ]
