@@ -26,7 +26,7 @@ OBJS      = $(BUILD)/gmm_kernels_i8.o $(BUILD)/gmm_kernels_f32.o $(BUILD)/gmm_ke
             $(BUILD)/gmm_kernels_presel.o $(BUILD)/gmm_presel.o $(BUILD)/gmm_kernels_shard.o $(BUILD)/gmm_hostio.o \
             $(BUILD)/gmm_kernels_direct.o $(BUILD)/gmm_kernels_layout.o $(BUILD)/gmm_shard.o $(BUILD)/gmm_kernels_pairs.o \
             $(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o \
-            $(BUILD)/gmm_kernels_accum.o $(BUILD)/gmm_estimator.o $(BUILD)/gmm_kernels_posterior.o \
+            $(BUILD)/gmm_kernels_accum.o $(BUILD)/gmm_kernels_accum_dual.o $(BUILD)/gmm_estimator.o $(BUILD)/gmm_kernels_posterior.o \
             $(BUILD)/gmm_kernels_state.o $(BUILD)/gmm_state.o \
             $(BUILD)/gmm_kernels_adapt.o $(BUILD)/gmm_adapt.o $(BUILD)/AffineTransformEstimate.o
 # include/rasr_gmm_estimator.h: the units behind it depend on these besides HDRS
@@ -39,8 +39,9 @@ REFSORT   = $(BUILD)/tests/refsort_test
 CLASSLAYOUT = $(BUILD)/tests/class_layout_test
 ESTCOMBINE = $(BUILD)/tests/estimator_combine_test
 AFFINEEST = $(BUILD)/tests/affine_estimate_test
+EBWEST   = $(BUILD)/tests/ebw_estimate_test
 
-all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) oracle check-integration
+all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) $(EBWEST) oracle check-integration
 
 $(BUILD)/gmm_kernels_i8.o: $(SRC)/gmm_kernels_i8.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -85,6 +86,12 @@ $(BUILD)/gmm_kernels_state.o: $(SRC)/gmm_kernels_state.hip $(HDRS)
 # maximum-likelihood accumulation (gmm_estimator_accumulate_*): resolve, inverted indexes (rocPRIM radix sort),
 # ordered f64 sums.  Not one of KERNEL_OBJS: gmm_kernel_id names the scoring kernels the PMC summaries measure
 $(BUILD)/gmm_kernels_accum.o: $(SRC)/gmm_kernels_accum.hip $(EST_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# joint numerator / denominator accumulation for discriminative training (gmm_estimator_accumulate_discriminative_*):
+# gmm_kernels_accum's passes with two f64 chains per lane.  Not one of KERNEL_OBJS
+$(BUILD)/gmm_kernels_accum_dual.o: $(SRC)/gmm_kernels_accum_dual.hip $(EST_HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -195,6 +202,13 @@ $(ESTCOMBINE): tests/cpp/estimator_combine_test.cc $(SRC)/host/MixtureSetEstimat
                $(HDRS) $(EST_HDRS)
 	@mkdir -p $(BUILD)/tests
 	g++ $(HOSTFLAGS) $(ESTCOMBINE_FLAGS) -o $@ $< $(SRC)/host/MixtureSetEstimatorFile.cc $(SRC)/host/MixtureSetFile.cc -lz
+
+# host check of the discriminative estimator file writer, gmm_estimator_combine_discriminative and
+# gmm_estimator_estimate_ebw (no GPU, no HIP): the two file units alone
+$(EBWEST): tests/cpp/ebw_estimate_test.cc $(SRC)/host/MixtureSetEstimatorFile.cc $(SRC)/host/MixtureSetFile.cc \
+            $(HDRS) $(EST_HDRS)
+	@mkdir -p $(BUILD)/tests
+	g++ $(HOSTFLAGS) $(EBWEST_FLAGS) -o $@ $< $(SRC)/host/MixtureSetEstimatorFile.cc $(SRC)/host/MixtureSetFile.cc -lz
 
 # host check of gmm_affine_estimate (no GPU, no HIP): the estimate unit alone
 $(AFFINEEST): tests/cpp/affine_estimate_test.cc $(SRC)/host/AffineTransformEstimate.cc include/rasr_gmm.h include/rasr_gmm_adaptation.h

@@ -8,7 +8,8 @@ from ._capi import (BATCH_DIAGONAL_MAXIMUM_FAST, BATCH_DIAGONAL_MAXIMUM_FLOAT, B
                     DEFAULT_WEIGHT_THRESHOLD, DIAGONAL_MAXIMUM, LIB_PATH, SCORER_TYPES, SIMD_DIAGONAL_MAXIMUM, STATE_POSTERIOR_CHUNK,
                     GmmError, load_library)
 from .adaptation import AffineTransformAccumulator, estimate_affine_transform
-from .estimator import Estimator, combine_estimators
+from .estimator import (Estimator, combine_discriminative_estimators, combine_estimators, ebw_config,
+                        ebw_iteration_constants, estimate_ebw)
 from .mixture_set import (MixtureSet, estimate_mixture_set, estimator_config, parse_mixture_set, ragged_counts,
                           read_mixture_set, synthetic_frames,
                           synthetic_mixture_set, write_mixture_set)
@@ -19,6 +20,7 @@ __all__ = [
     "SIMD_DIAGONAL_MAXIMUM", "SCORER_TYPES", "LIB_PATH", "GmmError", "load_library", "MixtureSet", "ragged_counts",
     "synthetic_frames", "synthetic_mixture_set", "Scorer", "default_config", "pinned_empty", "prepare_quantized_host",
     "read_mixture_set", "parse_mixture_set", "write_mixture_set", "estimate_mixture_set", "estimator_config",
-    "Estimator", "combine_estimators", "DEFAULT_WEIGHT_THRESHOLD", "STATE_POSTERIOR_CHUNK", "float_spread_bound",
+    "Estimator", "combine_estimators", "combine_discriminative_estimators", "estimate_ebw", "ebw_iteration_constants",
+    "ebw_config", "DEFAULT_WEIGHT_THRESHOLD", "STATE_POSTERIOR_CHUNK", "float_spread_bound",
     "AffineTransformAccumulator", "estimate_affine_transform",
 ]

@@ -106,6 +106,24 @@ class EstimatorConfig(ctypes.Structure):
     ]
 
 
+class EbwConfig(ctypes.Structure):  # gmm_ebw_config
+    _fields_ = [
+        ("minimum_observation_weight", ctypes.c_double),
+        ("minimum_relative_weight", ctypes.c_double),
+        ("minimum_variance", ctypes.c_double),
+        ("normalize_mixture_weights", ctypes.c_int),
+        ("iteration_constants_type", ctypes.c_int),
+        ("step_size", ctypes.c_double),
+        ("minimum_icd", ctypes.c_double),
+        ("beta", ctypes.c_double),
+        ("sigma_minimum", ctypes.c_double),
+        ("sigma_minimum_factor", ctypes.c_double),
+        ("number_of_iterations", ctypes.c_uint32),
+    ]
+
+
+EBW_TYPES = {"global-rwth": 0, "local-rwth": 1, "cambridge": 2}
+
 GMM_HOST_KEEP_BEST = 1
 GMM_HOST_FRAME_MAJOR = 2
 GMM_HOST_LAZY_BEST = 4
@@ -235,6 +253,37 @@ PROTOTYPES = [
     ("gmm_estimator_combine", ctypes.c_int,
      [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_void_p,
       ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    ("gmm_estimator_accumulate_discriminative_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("gmm_estimator_accumulate_discriminative_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    ("gmm_estimator_accumulate_discriminative_posteriors_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_double, ctypes.c_void_p]),
+    ("gmm_estimator_accumulate_discriminative_posteriors_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_double]),
+    ("gmm_estimator_accumulate_objective", ctypes.c_int, [ctypes.c_void_p, ctypes.c_double]),
+    ("gmm_estimator_objective", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]),
+    ("gmm_estimator_get_denominator", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("gmm_estimator_serialize_discriminative", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    ("gmm_estimator_write_discriminative", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
+    ("gmm_estimator_combine_discriminative", ctypes.c_int,
+     [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    ("gmm_default_ebw_config", None, [ctypes.POINTER(EbwConfig)]),
+    ("gmm_estimator_estimate_ebw", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(MixtureSetDesc), ctypes.POINTER(EbwConfig),
+      ctypes.POINTER(MixtureSetDesc)]),
+    ("gmm_estimator_ebw_iteration_constants", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(MixtureSetDesc), ctypes.POINTER(EbwConfig), ctypes.c_void_p,
+      ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    ("gmm_estimator_estimate_ebw_handle", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(MixtureSetDesc), ctypes.POINTER(EbwConfig), ctypes.POINTER(MixtureSetDesc)]),
     # include/rasr_gmm_adaptation.h
     ("gmm_affine_create", ctypes.c_int,
      [ctypes.POINTER(MixtureSetDesc), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),

@@ -37,6 +37,14 @@ struct gmm_estimator {
     DeviceBuffer<float>    dPostRows;
     DeviceBuffer<uint32_t> dContribFrame;
     DeviceBuffer<double>   dContribWeight;
+    // discriminative calls: the denominator tables (the numerator's shapes) and the second slab, allocated and zeroed
+    // by the handle's first discriminative call; the posterior form's second weight list with the posterior scratch
+    bool                 denominatorTables = false;
+    DeviceBuffer<double> dDenMeanSums, dDenMeanWeights, dDenCovSums, dDenCovWeights, dDenEntryWeights;
+    DeviceBuffer<double> dDenSlabSums, dDenSlabWeights, dPairWeightDen;
+    bool                 denominatorPosteriorScratch = false;
+    DeviceBuffer<double> dContribWeightDen;
+    double               objective = 0.0;  // objectiveFunction_ (host)
     // recorded by every accumulate call on its stream; get / skipped / serialize wait for it
     Event done;
     bool  pending = false;
@@ -52,6 +60,21 @@ uint32_t keyBits(uint32_t nDest) {
     return b;
 }
 
+int zeroDenominatorTables(gmm_estimator* e) {
+    const size_t D = e->D;
+    if (e->nMeans) {
+        GMM_HIP_CHECK(hipMemset(e->dDenMeanSums.get(), 0, e->nMeans * D * sizeof(double)));
+        GMM_HIP_CHECK(hipMemset(e->dDenMeanWeights.get(), 0, e->nMeans * sizeof(double)));
+    }
+    if (e->nCovs) {
+        GMM_HIP_CHECK(hipMemset(e->dDenCovSums.get(), 0, e->nCovs * D * sizeof(double)));
+        GMM_HIP_CHECK(hipMemset(e->dDenCovWeights.get(), 0, e->nCovs * sizeof(double)));
+    }
+    if (e->nEntries)
+        GMM_HIP_CHECK(hipMemset(e->dDenEntryWeights.get(), 0, e->nEntries * sizeof(double)));
+    return GMM_OK;
+}
+
 int zeroTables(gmm_estimator* e) {
     const size_t D = e->D;
     if (e->nMeans) {
@@ -65,6 +88,12 @@ int zeroTables(gmm_estimator* e) {
     if (e->nEntries)
         GMM_HIP_CHECK(hipMemset(e->dEntryWeights.get(), 0, e->nEntries * sizeof(double)));
     GMM_HIP_CHECK(hipMemset(e->dSkipped.get(), 0, sizeof(unsigned long long)));
+    if (e->denominatorTables) {
+        const int rc = zeroDenominatorTables(e);
+        if (rc != GMM_OK)
+            return rc;
+    }
+    e->objective = 0.0;
     GMM_HIP_CHECK(hipStreamSynchronize(nullptr));  // done before a call on any other stream
     return GMM_OK;
 }
@@ -320,6 +349,178 @@ int accumulatePosteriorsOn(gmm_estimator* e, gmm_scorer* scorer, const float* fr
                            stream);
 }
 
+// the denominator tables and the second slab, on the handle's first discriminative call
+int ensureDenominatorTables(gmm_estimator* e) {
+    if (e->denominatorTables)
+        return GMM_OK;
+    const size_t D = e->D, slots = accumSlabSlots(e->maxPairs);
+    GMM_HIP_CHECK(e->dDenMeanSums.alloc(e->nMeans * D));
+    GMM_HIP_CHECK(e->dDenMeanWeights.alloc(e->nMeans));
+    GMM_HIP_CHECK(e->dDenCovSums.alloc(e->nCovs * D));
+    GMM_HIP_CHECK(e->dDenCovWeights.alloc(e->nCovs));
+    GMM_HIP_CHECK(e->dDenEntryWeights.alloc(e->nEntries));
+    GMM_HIP_CHECK(e->dDenSlabSums.alloc(slots * D));
+    GMM_HIP_CHECK(e->dDenSlabWeights.alloc(slots));
+    GMM_HIP_CHECK(e->dPairWeightDen.alloc(e->maxPairs));
+    const int rc = zeroDenominatorTables(e);
+    if (rc != GMM_OK)
+        return rc;
+    GMM_HIP_CHECK(hipStreamSynchronize(nullptr));  // done before the call on any other stream
+    e->denominatorTables = true;
+    return GMM_OK;
+}
+
+int ensureDenominatorPosteriorScratch(gmm_estimator* e) {
+    if (e->denominatorPosteriorScratch)
+        return GMM_OK;
+    GMM_HIP_CHECK(e->dContribWeightDen.alloc(e->maxPairs));
+    e->denominatorPosteriorScratch = true;
+    return GMM_OK;
+}
+
+// accumulateKeyed with two accumulators per destination (gmm_kernels_accum_dual.hip): the same three sorts, once.
+// weightNum / weightDen are indexed by contribution, NaN where the contribution is not live on the side, NULL for a
+// side that receives nothing
+int accumulateKeyedDual(gmm_estimator* e, const float* frames, uint32_t frameStride, const uint32_t* pairFrame,
+                        const double* weightNum, const double* weightDen, uint32_t nPairs, hipStream_t stream) {
+    DualAccumArgs a{};
+    a.keysSorted     = e->dKeysSorted.get();
+    a.indexSorted    = e->dIndexSorted.get();
+    a.pairFrame      = pairFrame;
+    a.frames         = frames;
+    a.weight[0]      = weightNum;
+    a.weight[1]      = weightDen;
+    a.slabSums[0]    = e->dSlabSums.get();
+    a.slabSums[1]    = e->dDenSlabSums.get();
+    a.slabWeights[0] = e->dSlabWeights.get();
+    a.slabWeights[1] = e->dDenSlabWeights.get();
+    a.nPairs         = nPairs;
+    a.D              = e->D;
+    a.frameStride    = frameStride;
+    struct Index {
+        const uint32_t* keys;
+        uint32_t        nDest;
+        double *        sums, *weights, *denSums, *denWeights;
+        int             mode;
+    };
+    const Index indexes[3] = {
+            {e->dKeyMean.get(), e->nMeans, e->dMeanSums.get(), e->dMeanWeights.get(), e->dDenMeanSums.get(),
+             e->dDenMeanWeights.get(), kAccumSum},
+            {e->dKeyCov.get(), e->nCovs, e->dCovSums.get(), e->dCovWeights.get(), e->dDenCovSums.get(),
+             e->dDenCovWeights.get(), kAccumSquare},
+            {e->dKeyEntry.get(), e->nEntries, nullptr, e->dEntryWeights.get(), nullptr, e->dDenEntryWeights.get(),
+             kAccumWeightOnly}};
+    for (const Index& x : indexes) {
+        if (x.nDest == 0)
+            continue;
+        GMM_HIP_CHECK(static_cast<hipError_t>(launchAccumSort(e->dSortTemp.get(), e->sortTempBytes, x.keys, e->dPairIndex.get(),
+                                                             e->dKeysSorted.get(), e->dIndexSorted.get(), nPairs,
+                                                             keyBits(x.nDest), stream)));
+        a.nDest      = x.nDest;
+        a.sums[0]    = x.sums;
+        a.sums[1]    = x.denSums;
+        a.weights[0] = x.weights;
+        a.weights[1] = x.denWeights;
+        a.mode       = x.mode;
+        GMM_HIP_CHECK(static_cast<hipError_t>(launchAccumulateSegmentsDual(a, stream)));
+        GMM_HIP_CHECK(static_cast<hipError_t>(launchCombinePiecesDual(a, stream)));
+    }
+    return GMM_OK;
+}
+
+// the joint Viterbi call: accumulateOn with two weight lists
+int accumulateDiscriminativeOn(gmm_estimator* e, gmm_scorer* scorer, const float* frames, uint32_t nFrames,
+                               uint32_t frameStride, const uint32_t* pairFrame, const uint32_t* pairMix,
+                               const uint32_t* pairDensity, const double* weightNum, const double* weightDen,
+                               uint32_t nPairs, hipStream_t stream) {
+    if (!pairDensity && scorer) {  // the Viterbi branch: densityIndex() = bestDensity of the pair
+        PairArgs a  = pairArgsOf(scorer, frames, nFrames, frameStride);
+        a.pairFrame = pairFrame;
+        a.pairMix   = pairMix;
+        a.best      = e->dBest.get();
+        a.nPairs    = nPairs;
+        GMM_HIP_CHECK(launchBestPairs(a, stream));
+        pairDensity = e->dBest.get();
+    }
+    DualResolveArgs q{};
+    ResolveArgs&    r = q.r;
+    r.pairFrame       = pairFrame;
+    r.pairMix         = pairMix;
+    r.pairDensity     = pairDensity;
+    r.mixOff          = e->dMixOff.get();
+    r.entryMean       = e->dEntryMean.get();
+    r.entryCov        = e->dEntryCov.get();
+    r.keyMean         = e->dKeyMean.get();
+    r.keyCov          = e->dKeyCov.get();
+    r.keyEntry        = e->dKeyEntry.get();
+    r.pairIndex       = e->dPairIndex.get();
+    r.skipped         = e->dSkipped.get();
+    r.nPairs          = nPairs;
+    r.nFrames         = nFrames;
+    r.nMix            = e->nMix;
+    r.nMeans          = e->nMeans;
+    r.nCovs           = e->nCovs;
+    r.nEntries        = e->nEntries;
+    q.weightNum       = weightNum;
+    q.weightDen       = weightDen;
+    GMM_HIP_CHECK(static_cast<hipError_t>(launchResolvePairsDual(q, stream)));
+    return accumulateKeyedDual(e, frames, frameStride, pairFrame, weightNum, weightDen, nPairs, stream);
+}
+
+// the joint Baum-Welch call: the posterior rows once (the kernel of gmm_density_posteriors_pairs_device), their
+// expansion into contribution slots with one finalWeight per side, then the dual keyed tail
+int accumulateDiscriminativePosteriorsOn(gmm_estimator* e, gmm_scorer* scorer, const float* frames, uint32_t nFrames,
+                                         uint32_t frameStride, const uint32_t* pairFrame, const uint32_t* pairMix,
+                                         const double* weightNum, const double* weightDen, uint32_t nPairs,
+                                         double threshold, hipStream_t stream) {
+    const uint32_t rowStride = scorer ? e->maxEntries : 1u;
+    if (scorer) {
+        PosteriorArgs q{};
+        q.pair           = pairArgsOf(scorer, frames, nFrames, frameStride);
+        q.pair.pairFrame = pairFrame;
+        q.pair.pairMix   = pairMix;
+        q.pair.nPairs    = nPairs;
+        q.posteriors     = e->dPostRows.get();
+        q.rowStride      = rowStride;
+        GMM_HIP_CHECK(launchDensityPosteriors(q, stream));
+    }
+    DualExpandArgs x{};
+    x.pairFrame        = pairFrame;
+    x.pairMix          = pairMix;
+    x.weightNum        = weightNum;
+    x.weightDen        = weightDen;
+    x.posteriors       = scorer ? e->dPostRows.get() : nullptr;
+    x.mixOff           = e->dMixOff.get();
+    x.entryMean        = e->dEntryMean.get();
+    x.entryCov         = e->dEntryCov.get();
+    x.keyMean          = e->dKeyMean.get();
+    x.keyCov           = e->dKeyCov.get();
+    x.keyEntry         = e->dKeyEntry.get();
+    x.contribIndex     = e->dPairIndex.get();
+    x.contribFrame     = e->dContribFrame.get();
+    x.contribWeightNum = e->dContribWeight.get();
+    x.contribWeightDen = e->dContribWeightDen.get();
+    x.skipped          = e->dSkipped.get();
+    x.threshold        = threshold;
+    x.nPairs           = nPairs;
+    x.rowStride        = rowStride;
+    x.nFrames          = nFrames;
+    x.nMix             = e->nMix;
+    x.nMeans           = e->nMeans;
+    x.nCovs            = e->nCovs;
+    x.nEntries         = e->nEntries;
+    GMM_HIP_CHECK(static_cast<hipError_t>(launchExpandDual(x, stream)));
+    return accumulateKeyedDual(e, frames, frameStride, e->dContribFrame.get(), weightNum ? e->dContribWeight.get() : nullptr,
+                               weightDen ? e->dContribWeightDen.get() : nullptr, nPairs * rowStride, stream);
+}
+
+// the checks of a discriminative call that need no device, and what its first call on a handle allocates
+int checkSides(const double* weightNum, const double* weightDen) {
+    if (!weightNum && !weightDen)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "pair_weight_num and pair_weight_den are both NULL: the call has no side to add to");
+    return GMM_OK;
+}
+
 // host copies of the tables, after the last call
 struct HostTables {
     std::vector<double> meanSums, meanWeights, covSums, covWeights, entryWeights;
@@ -343,7 +544,32 @@ int fetch(gmm_estimator* e, double* meanSums, double* meanWeights, double* covSu
     return GMM_OK;
 }
 
-int serialize(gmm_estimator* e, std::vector<unsigned char>& bytes) {
+// the denominator tables; zeros for a handle that has seen no discriminative call (they are not allocated then)
+int fetchDenominator(gmm_estimator* e, double* meanSums, double* meanWeights, double* covSums, double* covWeights,
+                     double* entryWeights) {
+    GMM_HIP_CHECK(hipSetDevice(e->device));
+    const int rc = waitDone(e);
+    if (rc != GMM_OK)
+        return rc;
+    const size_t D = e->D;
+    const struct {
+        double*       dst;
+        const double* src;
+        size_t        n;
+    } copies[5] = {{meanSums, e->dDenMeanSums.get(), e->nMeans * D}, {meanWeights, e->dDenMeanWeights.get(), e->nMeans},
+                   {covSums, e->dDenCovSums.get(), e->nCovs * D},    {covWeights, e->dDenCovWeights.get(), e->nCovs},
+                   {entryWeights, e->dDenEntryWeights.get(), e->nEntries}};
+    for (const auto& c : copies)
+        if (c.dst && c.n) {
+            if (e->denominatorTables)
+                GMM_HIP_CHECK(hipMemcpy(c.dst, c.src, c.n * sizeof(double), hipMemcpyDeviceToHost));
+            else
+                std::fill(c.dst, c.dst + c.n, 0.0);
+        }
+    return GMM_OK;
+}
+
+int serialize(gmm_estimator* e, std::vector<unsigned char>& bytes, bool discriminative = false) {
     HostTables h;
     h.meanSums.resize(static_cast<size_t>(e->nMeans) * e->D);
     h.meanWeights.resize(e->nMeans);
@@ -368,7 +594,49 @@ int serialize(gmm_estimator* e, std::vector<unsigned char>& bytes) {
     t.covSums      = h.covSums.data();
     t.covWeights   = h.covWeights.data();
     t.entryWeights = h.entryWeights.data();
-    bytes          = writeEstimatorFile(t);
+    if (!discriminative) {
+        bytes = writeEstimatorFile(t);
+        return GMM_OK;
+    }
+    HostTables d;
+    d.meanSums.resize(h.meanSums.size());
+    d.meanWeights.resize(h.meanWeights.size());
+    d.covSums.resize(h.covSums.size());
+    d.covWeights.resize(h.covWeights.size());
+    d.entryWeights.resize(h.entryWeights.size());
+    const int rd = fetchDenominator(e, d.meanSums.data(), d.meanWeights.data(), d.covSums.data(), d.covWeights.data(),
+                                    d.entryWeights.data());
+    if (rd != GMM_OK)
+        return rd;
+    DenominatorTables den{};
+    den.meanSums     = d.meanSums.data();
+    den.meanWeights  = d.meanWeights.data();
+    den.covSums      = d.covSums.data();
+    den.covWeights   = d.covWeights.data();
+    den.entryWeights = d.entryWeights.data();
+    den.objective    = e->objective;
+    bytes            = writeDiscriminativeEstimatorFile(t, den);
+    return GMM_OK;
+}
+
+int copyBytesOut(const std::vector<unsigned char>& bytes, void* data, uint64_t capacity, uint64_t* size) {
+    *size = bytes.size();
+    if (!data)
+        return GMM_OK;
+    if (capacity < bytes.size())
+        return fail(GMM_ERR_CAPACITY, "estimator file of " + std::to_string(bytes.size()) + " bytes, capacity " +
+                                              std::to_string(capacity));
+    std::memcpy(data, bytes.data(), bytes.size());
+    return GMM_OK;
+}
+
+int writeBytes(const std::vector<unsigned char>& bytes, const char* filename) {
+    std::FILE* f = std::fopen(filename, "wb");
+    if (!f)
+        return fail(GMM_ERR_INVALID_ARGUMENT, std::string("estimator file: cannot open \"") + filename + "\" for writing");
+    const bool ok = std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    if (std::fclose(f) != 0 || !ok)
+        return fail(GMM_ERR_INVALID_ARGUMENT, std::string("estimator file: error writing \"") + filename + "\"");
     return GMM_OK;
 }
 
@@ -496,6 +764,163 @@ int gmm_estimator_accumulate_posteriors_host(gmm_estimator* e, gmm_scorer* score
     return rc;
 }
 
+int gmm_estimator_accumulate_discriminative_device(gmm_estimator* e, gmm_scorer* scorer, const float* frames,
+                                                   uint32_t nFrames, uint32_t frameStride, const uint32_t* pairFrame,
+                                                   const uint32_t* pairMix, const uint32_t* pairDensity,
+                                                   const double* weightNum, const double* weightDen, uint32_t nPairs,
+                                                   void* stream) {
+    int rc = checkCall(e, scorer, frames, frameStride, pairFrame, pairMix, pairDensity, nPairs);
+    if (rc == GMM_OK)
+        rc = checkSides(weightNum, weightDen);
+    if (rc != GMM_OK)
+        return rc;
+    GMM_HIP_CHECK(hipSetDevice(e->device));
+    if ((rc = ensureDenominatorTables(e)) != GMM_OK || nPairs == 0)
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = accumulateDiscriminativeOn(e, scorer, frames, nFrames, frameStride, pairFrame, pairMix, pairDensity, weightNum,
+                                    weightDen, nPairs, st);
+    GMM_HIP_CHECK(hipEventRecord(e->done.get(), st));
+    e->pending = true;
+    return rc;
+}
+
+int gmm_estimator_accumulate_discriminative_host(gmm_estimator* e, gmm_scorer* scorer, const float* frames,
+                                                 uint32_t nFrames, uint32_t frameStride, const uint32_t* pairFrame,
+                                                 const uint32_t* pairMix, const uint32_t* pairDensity,
+                                                 const double* weightNum, const double* weightDen, uint32_t nPairs) {
+    int rc = checkCall(e, scorer, frames, frameStride, pairFrame, pairMix, pairDensity, nPairs);
+    if (rc == GMM_OK)
+        rc = checkSides(weightNum, weightDen);
+    if (rc != GMM_OK)
+        return rc;
+    GMM_HIP_CHECK(hipSetDevice(e->device));
+    if ((rc = waitDone(e)) != GMM_OK || (rc = ensureDenominatorTables(e)) != GMM_OK || nPairs == 0)
+        return rc;
+    DeviceBuffer<float> dFrames;
+    const size_t        D = e->D, n = nPairs;
+    GMM_HIP_CHECK(dFrames.alloc(std::max<size_t>(static_cast<size_t>(nFrames) * D, 1)));
+    if (nFrames && D)
+        GMM_HIP_CHECK(hipMemcpy2D(dFrames.get(), D * sizeof(float), frames, static_cast<size_t>(frameStride) * sizeof(float),
+                                  D * sizeof(float), nFrames, hipMemcpyHostToDevice));
+    GMM_HIP_CHECK(hipMemcpy(e->dPairFrame.get(), pairFrame, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    GMM_HIP_CHECK(hipMemcpy(e->dPairMix.get(), pairMix, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (pairDensity)
+        GMM_HIP_CHECK(hipMemcpy(e->dPairDensity.get(), pairDensity, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (weightNum)
+        GMM_HIP_CHECK(hipMemcpy(e->dPairWeight.get(), weightNum, n * sizeof(double), hipMemcpyHostToDevice));
+    if (weightDen)
+        GMM_HIP_CHECK(hipMemcpy(e->dPairWeightDen.get(), weightDen, n * sizeof(double), hipMemcpyHostToDevice));
+    rc = accumulateDiscriminativeOn(e, scorer, dFrames.get(), nFrames, e->D, e->dPairFrame.get(), e->dPairMix.get(),
+                                    pairDensity ? e->dPairDensity.get() : nullptr, weightNum ? e->dPairWeight.get() : nullptr,
+                                    weightDen ? e->dPairWeightDen.get() : nullptr, nPairs, nullptr);
+    GMM_HIP_CHECK(hipStreamSynchronize(nullptr));  // before dFrames is released
+    return rc;
+}
+
+int gmm_estimator_accumulate_discriminative_posteriors_device(gmm_estimator* e, gmm_scorer* scorer, const float* frames,
+                                                              uint32_t nFrames, uint32_t frameStride,
+                                                              const uint32_t* pairFrame, const uint32_t* pairMix,
+                                                              const double* weightNum, const double* weightDen,
+                                                              uint32_t nPairs, double threshold, void* stream) {
+    int rc = checkPosteriorCall(e, scorer, frames, frameStride, pairFrame, pairMix, nPairs);
+    if (rc == GMM_OK)
+        rc = checkSides(weightNum, weightDen);
+    if (rc != GMM_OK)
+        return rc;
+    GMM_HIP_CHECK(hipSetDevice(e->device));
+    if ((rc = ensureDenominatorTables(e)) != GMM_OK || nPairs == 0)
+        return rc;
+    if ((rc = ensurePosteriorScratch(e)) != GMM_OK || (rc = ensureDenominatorPosteriorScratch(e)) != GMM_OK)
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = accumulateDiscriminativePosteriorsOn(e, scorer, frames, nFrames, frameStride, pairFrame, pairMix, weightNum,
+                                              weightDen, nPairs, threshold, st);
+    GMM_HIP_CHECK(hipEventRecord(e->done.get(), st));
+    e->pending = true;
+    return rc;
+}
+
+int gmm_estimator_accumulate_discriminative_posteriors_host(gmm_estimator* e, gmm_scorer* scorer, const float* frames,
+                                                            uint32_t nFrames, uint32_t frameStride,
+                                                            const uint32_t* pairFrame, const uint32_t* pairMix,
+                                                            const double* weightNum, const double* weightDen,
+                                                            uint32_t nPairs, double threshold) {
+    int rc = checkPosteriorCall(e, scorer, frames, frameStride, pairFrame, pairMix, nPairs);
+    if (rc == GMM_OK)
+        rc = checkSides(weightNum, weightDen);
+    if (rc != GMM_OK)
+        return rc;
+    GMM_HIP_CHECK(hipSetDevice(e->device));
+    if ((rc = waitDone(e)) != GMM_OK || (rc = ensureDenominatorTables(e)) != GMM_OK || nPairs == 0)
+        return rc;
+    if ((rc = ensurePosteriorScratch(e)) != GMM_OK || (rc = ensureDenominatorPosteriorScratch(e)) != GMM_OK)
+        return rc;
+    DeviceBuffer<float> dFrames;
+    const size_t        D = e->D, n = nPairs;
+    GMM_HIP_CHECK(dFrames.alloc(std::max<size_t>(static_cast<size_t>(nFrames) * D, 1)));
+    if (nFrames && D)
+        GMM_HIP_CHECK(hipMemcpy2D(dFrames.get(), D * sizeof(float), frames, static_cast<size_t>(frameStride) * sizeof(float),
+                                  D * sizeof(float), nFrames, hipMemcpyHostToDevice));
+    GMM_HIP_CHECK(hipMemcpy(e->dPairFrame.get(), pairFrame, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    GMM_HIP_CHECK(hipMemcpy(e->dPairMix.get(), pairMix, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (weightNum)
+        GMM_HIP_CHECK(hipMemcpy(e->dPairWeight.get(), weightNum, n * sizeof(double), hipMemcpyHostToDevice));
+    if (weightDen)
+        GMM_HIP_CHECK(hipMemcpy(e->dPairWeightDen.get(), weightDen, n * sizeof(double), hipMemcpyHostToDevice));
+    rc = accumulateDiscriminativePosteriorsOn(e, scorer, dFrames.get(), nFrames, e->D, e->dPairFrame.get(), e->dPairMix.get(),
+                                              weightNum ? e->dPairWeight.get() : nullptr,
+                                              weightDen ? e->dPairWeightDen.get() : nullptr, nPairs, threshold, nullptr);
+    GMM_HIP_CHECK(hipStreamSynchronize(nullptr));  // before dFrames is released
+    return rc;
+}
+
+int gmm_estimator_accumulate_objective(gmm_estimator* e, double f) {
+    if (!e)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null estimator");
+    e->objective += f;  // objectiveFunction_ += (Sum) f
+    return GMM_OK;
+}
+
+int gmm_estimator_objective(gmm_estimator* e, double* objective) {
+    if (!e || !objective)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null argument");
+    *objective = e->objective;
+    return GMM_OK;
+}
+
+int gmm_estimator_get_denominator(gmm_estimator* e, double* meanSums, double* meanWeights, double* covSums,
+                                  double* covWeights, double* entryWeights) {
+    if (!e)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null estimator");
+    return fetchDenominator(e, meanSums, meanWeights, covSums, covWeights, entryWeights);
+}
+
+int gmm_estimator_serialize_discriminative(gmm_estimator* e, void* data, uint64_t capacity, uint64_t* size) {
+    if (!e || !size)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<unsigned char> bytes;
+    const int                  rc = serialize(e, bytes, true);
+    return rc != GMM_OK ? rc : copyBytesOut(bytes, data, capacity, size);
+}
+
+int gmm_estimator_write_discriminative(gmm_estimator* e, const char* filename) {
+    if (!e || !filename)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<unsigned char> bytes;
+    const int                  rc = serialize(e, bytes, true);
+    return rc != GMM_OK ? rc : writeBytes(bytes, filename);
+}
+
+int gmm_estimator_estimate_ebw_handle(gmm_estimator* e, const gmm_mixture_set* previous, const gmm_ebw_config* config,
+                                      gmm_mixture_set* out) {
+    if (!e || !out)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<unsigned char> bytes;
+    const int                  rc = serialize(e, bytes, true);
+    return rc != GMM_OK ? rc : gmm_estimator_estimate_ebw(bytes.data(), bytes.size(), previous, config, out);
+}
+
 int gmm_estimator_skipped(gmm_estimator* e, uint64_t* skipped) {
     if (!e || !skipped)
         return fail(GMM_ERR_INVALID_ARGUMENT, "null argument");
@@ -523,14 +948,7 @@ int gmm_estimator_serialize(gmm_estimator* e, void* data, uint64_t capacity, uin
     const int                  rc = serialize(e, bytes);
     if (rc != GMM_OK)
         return rc;
-    *size = bytes.size();
-    if (!data)
-        return GMM_OK;
-    if (capacity < bytes.size())
-        return fail(GMM_ERR_CAPACITY, "estimator file of " + std::to_string(bytes.size()) + " bytes, capacity " +
-                                              std::to_string(capacity));
-    std::memcpy(data, bytes.data(), bytes.size());
-    return GMM_OK;
+    return copyBytesOut(bytes, data, capacity, size);
 }
 
 int gmm_estimator_write(gmm_estimator* e, const char* filename) {
@@ -540,13 +958,7 @@ int gmm_estimator_write(gmm_estimator* e, const char* filename) {
     const int                  rc = serialize(e, bytes);
     if (rc != GMM_OK)
         return rc;
-    std::FILE* f = std::fopen(filename, "wb");
-    if (!f)
-        return fail(GMM_ERR_INVALID_ARGUMENT, std::string("estimator file: cannot open \"") + filename + "\" for writing");
-    const bool ok = std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
-    if (std::fclose(f) != 0 || !ok)
-        return fail(GMM_ERR_INVALID_ARGUMENT, std::string("estimator file: error writing \"") + filename + "\"");
-    return GMM_OK;
+    return writeBytes(bytes, filename);
 }
 
 int gmm_estimator_estimate(gmm_estimator* e, const gmm_estimator_config* config, gmm_mixture_set* out) {

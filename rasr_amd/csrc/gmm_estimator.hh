@@ -63,6 +63,59 @@ struct AccumArgs {
 int launchAccumulateSegments(const AccumArgs& a, ihipStream_t* stream);
 int launchCombinePieces(const AccumArgs& a, ihipStream_t* stream);
 
+// ---- the joint numerator / denominator passes (gmm_kernels_accum_dual.hip) ----
+// A side's weight array holds NaN where the contribution is not live on that side; a NULL array is a side that
+// receives nothing from the call.
+
+// pass 1, Viterbi form: resolvePairs' keys; a good pair live on neither side gets the sentinel keys and is not counted
+struct DualResolveArgs {
+    ResolveArgs   r;
+    const double* weightNum;  // [nPairs] or NULL
+    const double* weightDen;  // [nPairs] or NULL
+};
+int launchResolvePairsDual(const DualResolveArgs& a, ihipStream_t* stream);
+
+// pass 1, Baum-Welch form: the posterior rows (gmm_density_posteriors_pairs_device's, computed once) expanded into
+// contribution slots c = pair * rowStride + j with one finalWeight per side (NaN where not above the threshold)
+struct DualExpandArgs {
+    const uint32_t* pairFrame;   // [nPairs]
+    const uint32_t* pairMix;     // [nPairs]
+    const double*   weightNum;   // [nPairs] or NULL
+    const double*   weightDen;   // [nPairs] or NULL
+    const float*    posteriors;  // [nPairs][rowStride], or NULL: one density per mixture, posterior 1
+    const uint32_t* mixOff;      // [nMix + 1]
+    const uint32_t* entryMean;   // [nEntries]
+    const uint32_t* entryCov;    // [nEntries]
+    uint32_t*       keyMean;     // [nPairs * rowStride] out
+    uint32_t*       keyCov;
+    uint32_t*       keyEntry;
+    uint32_t*       contribIndex;      // out: 0, 1, ...
+    uint32_t*       contribFrame;      // out
+    double*         contribWeightNum;  // out (written only for a given side)
+    double*         contribWeightDen;
+    unsigned long long* skipped;       // += bad pairs, once each
+    double          threshold;
+    uint32_t        nPairs, rowStride, nFrames, nMix, nMeans, nCovs, nEntries;
+};
+int launchExpandDual(const DualExpandArgs& a, ihipStream_t* stream);
+
+// passes 3 and 4 over one inverted index, two accumulators per destination
+struct DualAccumArgs {
+    const uint32_t* keysSorted;   // as AccumArgs
+    const uint32_t* indexSorted;
+    const uint32_t* pairFrame;
+    const float*    frames;
+    const double*   weight[2];       // per contribution, NaN: not live on the side; NULL: the side takes no part
+    double*         sums[2];         // [nDest][D] (NULL for kAccumWeightOnly)
+    double*         weights[2];      // [nDest]
+    double*         slabSums[2];     // [accumSlabSlots][D]
+    double*         slabWeights[2];  // [accumSlabSlots]
+    uint32_t        nPairs, nDest, D, frameStride;
+    int             mode;  // AccumMode
+};
+int launchAccumulateSegmentsDual(const DualAccumArgs& a, ihipStream_t* stream);
+int launchCombinePiecesDual(const DualAccumArgs& a, ihipStream_t* stream);
+
 // ---- the file format (host/MixtureSetEstimatorFile.cc) ----
 
 // an estimator's topology and host copies of its tables
@@ -80,5 +133,18 @@ struct EstimatorTables {
 };
 // AbstractMixtureSetEstimator::write (cc:416-420, 481-509) with MixtureSetEstimatorIndexMap's numbering (cc:804-817)
 std::vector<unsigned char> writeEstimatorFile(const EstimatorTables& t);
+
+// the denominator tables (laid out as the numerator's in EstimatorTables) and the objective function
+struct DenominatorTables {
+    const double* meanSums;
+    const double* meanWeights;
+    const double* covSums;
+    const double* covWeights;
+    const double* entryWeights;
+    double        objective;
+};
+// EbwDiscriminativeMixtureSetEstimator::write: writeEstimatorFile's bytes with every mean and covariance followed by
+// its denominator accumulator, every mixture's entries by its denominator weights, the objective function last
+std::vector<unsigned char> writeDiscriminativeEstimatorFile(const EstimatorTables& t, const DenominatorTables& den);
 
 }  // namespace rasr_gmm

@@ -18,6 +18,20 @@
 //   AbstractMixtureSetEstimator::write         src/Mm/AbstractMixtureSetEstimator.cc:416-420, 481-509
 // and gmm_estimator_combine the trainer's combine action over several of them,
 //   accumulate(Core::BinaryInputStreams&, os)  src/Mm/AbstractMixtureSetEstimator.cc:171-290.
+// The discriminative (EBW) estimator's file is the same layout, same magic and version 2, with
+//   EbwDiscriminativeMeanEstimator::write        src/Mm/EbwDiscriminativeGaussDensityEstimator.cc:55-58   every mean's
+//                                                accumulator followed by its denominator accumulator
+//   EbwDiscriminativeCovarianceEstimator::write  cc:150-153   every covariance likewise
+//   EbwDiscriminativeMixtureEstimator::write     src/Mm/EbwDiscriminativeMixtureEstimator.cc:148-154   a mixture's
+//                                                (density, weight) entries followed by its f64 denominator weights
+//   DiscriminativeMixtureSetEstimator::write     src/Mm/DiscriminativeMixtureSetEstimator.cc:115-119   the f64 objective
+//                                                function as the file's last field (read for version > 1, cc:105-113)
+// (writeDiscriminativeEstimatorFile), combined by gmm_estimator_combine_discriminative as in
+//   EbwDiscriminativeMean/CovarianceEstimator::accumulate  EbwDiscriminativeGaussDensityEstimator.cc:40-44, 135-139
+//   EbwDiscriminativeMixtureEstimator::accumulate(is, os)  EbwDiscriminativeMixtureEstimator.cc:172-186
+//   DiscriminativeMixtureSetEstimator::accumulate(is, os)  DiscriminativeMixtureSetEstimator.cc:162-177.
+// Nothing in the header tells the two formats apart: the discriminative reader refuses a file that does not parse as
+// one to its last byte (a maximum-likelihood file does not).
 //
 // The arithmetic follows the reference in f64 with the reference's operation order, results stored as
 // f32 means / variances and f64 log weights.  One order is not defined by the reference: the covariance
@@ -85,6 +99,7 @@ struct DensityEst {
 struct MixtureEst {
     std::vector<uint32_t> dens;     // density estimator indices
     std::vector<double>   weights;  // Weight per density
+    std::vector<double>   denWeights;  // denWeights_ (discriminative files)
     double                weight() const {  // getWeight: std::accumulate(..., 0.0)
         double s = 0.0;
         for (double w : weights)
@@ -157,12 +172,14 @@ struct Writer {  // Core::BinaryOutputStream into a byte vector
 struct EstimatorFile {
     uint32_t                 version = 0, dimension = 0;
     std::vector<Accumulator> means, covs;
+    std::vector<Accumulator> denMeans, denCovs;  // discriminative files: the denominator accumulators
     std::vector<DensityEst>  dens;
     std::vector<MixtureEst>  mix;
+    double                   objective = 0;  // discriminative files
 };
 
 // "" or what is wrong with the file
-std::string readEstimatorFile(const void* data, uint64_t size, EstimatorFile& f) {
+std::string readEstimatorFile(const void* data, uint64_t size, EstimatorFile& f, bool discriminative = false) {
     static const unsigned char empty = 0;
     const unsigned char* b = data ? static_cast<const unsigned char*>(data) : &empty;
     Reader r{b, b + (data ? size : 0)};
@@ -173,11 +190,17 @@ std::string readEstimatorFile(const void* data, uint64_t size, EstimatorFile& f)
         return "magic \"MIXSET\" expected";
     f.version   = r.get<uint32_t>();
     f.dimension = r.get<uint32_t>();
-    for (std::vector<Accumulator>* accs : {&f.means, &f.covs}) {
-        const uint32_t n = r.get<uint32_t>();
+    for (int which = 0; which < 2; ++which) {
+        std::vector<Accumulator>& accs = which ? f.covs : f.means;
+        std::vector<Accumulator>& den  = which ? f.denCovs : f.denMeans;
+        const uint32_t            n    = r.get<uint32_t>();
         for (uint32_t i = 0; i < n && !r.fail; ++i) {
-            accs->emplace_back();
-            accs->back().read(r, f.version);
+            accs.emplace_back();
+            accs.back().read(r, f.version);
+            if (discriminative && !r.fail) {
+                den.emplace_back();
+                den.back().read(r, f.version);
+            }
         }
     }
     const uint32_t nDens = r.get<uint32_t>();
@@ -185,6 +208,8 @@ std::string readEstimatorFile(const void* data, uint64_t size, EstimatorFile& f)
         DensityEst d;
         d.mean = r.get<uint32_t>();
         d.cov  = r.get<uint32_t>();
+        if (!r.fail && discriminative && (d.mean >= f.means.size() || d.cov >= f.covs.size()))
+            return "a density refers to a mean or covariance out of range";
         f.dens.push_back(d);
     }
     const uint32_t nMix = r.get<uint32_t>();
@@ -198,12 +223,21 @@ std::string readEstimatorFile(const void* data, uint64_t size, EstimatorFile& f)
         for (uint32_t j = 0; j < n && !r.fail; ++j) {
             x.dens.push_back(r.get<uint32_t>());
             x.weights.push_back(f.version > 0 ? r.get<double>() : static_cast<double>(r.get<uint32_t>()));
+            if (!r.fail && discriminative && x.dens.back() >= nDens)
+                return "a mixture refers to a density out of range";
         }
+        if (discriminative)
+            for (uint32_t j = 0; j < n && !r.fail; ++j)
+                x.denWeights.push_back(r.get<double>());
         f.mix.push_back(std::move(x));
     }
+    if (discriminative && f.version > 1)
+        f.objective = r.get<double>();
     if (r.fail)
         return "truncated file";
-    for (const std::vector<Accumulator>* accs : {&f.means, &f.covs})
+    if (discriminative && r.p != r.end)
+        return "bytes left after the objective function: not a discriminative estimator file";
+    for (const std::vector<Accumulator>* accs : {&f.means, &f.covs, &f.denMeans, &f.denCovs})
         for (const Accumulator& a : *accs)
             if (a.sum.size() != f.dimension)
                 return "an accumulator's size differs from the dimension";
@@ -245,6 +279,46 @@ std::vector<unsigned char> writeEstimatorFile(const EstimatorTables& t) {
             w.put<double>(t.entryWeights[e]);
         }
     }
+    return std::move(w.bytes);
+}
+
+std::vector<unsigned char> writeDiscriminativeEstimatorFile(const EstimatorTables& t, const DenominatorTables& den) {
+    IndexMap meanMap(t.nMeans), covMap(t.nCovs), densMap(t.nDens);
+    for (uint32_t e = 0; e < t.mixOff[t.nMix]; ++e) {
+        const uint32_t d = t.mixDens[e];
+        meanMap.add(t.dnsMean[d]);
+        covMap.add(t.dnsCov[d]);
+        densMap.add(d);
+    }
+    const size_t D = t.D;
+    Writer       w;
+    w.header(t.D);
+    w.put<uint32_t>(static_cast<uint32_t>(meanMap.order.size()));
+    for (uint32_t m : meanMap.order) {  // EbwDiscriminativeMeanEstimator::write: Precursor, then denAccumulator_
+        w.accumulator(t.meanSums + m * D, D, t.meanWeights[m]);
+        w.accumulator(den.meanSums + m * D, D, den.meanWeights[m]);
+    }
+    w.put<uint32_t>(static_cast<uint32_t>(covMap.order.size()));
+    for (uint32_t c : covMap.order) {  // EbwDiscriminativeCovarianceEstimator::write
+        w.accumulator(t.covSums + c * D, D, t.covWeights[c]);
+        w.accumulator(den.covSums + c * D, D, den.covWeights[c]);
+    }
+    w.put<uint32_t>(static_cast<uint32_t>(densMap.order.size()));
+    for (uint32_t d : densMap.order) {
+        w.put<uint32_t>(static_cast<uint32_t>(meanMap.index[t.dnsMean[d]]));
+        w.put<uint32_t>(static_cast<uint32_t>(covMap.index[t.dnsCov[d]]));
+    }
+    w.put<uint32_t>(t.nMix);
+    for (uint32_t m = 0; m < t.nMix; ++m) {  // EbwDiscriminativeMixtureEstimator::write: Precursor, then denWeights_
+        w.put<uint32_t>(t.mixOff[m + 1] - t.mixOff[m]);
+        for (uint32_t e = t.mixOff[m]; e < t.mixOff[m + 1]; ++e) {
+            w.put<uint32_t>(static_cast<uint32_t>(densMap.index[t.mixDens[e]]));
+            w.put<double>(t.entryWeights[e]);
+        }
+        for (uint32_t e = t.mixOff[m]; e < t.mixOff[m + 1]; ++e)
+            w.put<double>(den.entryWeights[e]);
+    }
+    w.put<double>(den.objective);  // DiscriminativeMixtureSetEstimator::write: os << (Sum) objectiveFunction()
     return std::move(w.bytes);
 }
 
@@ -479,8 +553,8 @@ int gmm_mixture_set_estimate(const void* data, uint64_t size, const gmm_estimato
     return GMM_OK;
 }
 
-int gmm_estimator_combine(const void* const* data, const uint64_t* size, uint32_t n, void* out, uint64_t capacity,
-                          uint64_t* outSize) {
+static int combineFiles(const void* const* data, const uint64_t* size, uint32_t n, void* out, uint64_t capacity,
+                        uint64_t* outSize, bool discriminative) {
     if (!data || !size || !outSize)
         return fail(GMM_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0)
@@ -489,7 +563,7 @@ int gmm_estimator_combine(const void* const* data, const uint64_t* size, uint32_
     for (uint32_t i = 0; i < n; ++i) {
         EstimatorFile     f;
         const std::string where = "combine: file " + std::to_string(i) + ": ";
-        const std::string err   = readEstimatorFile(data[i], size[i], f);
+        const std::string err   = readEstimatorFile(data[i], size[i], f, discriminative);
         if (!err.empty())
             return fail(GMM_ERR_INVALID_ARGUMENT, where + err);
         if (i == 0) {  // the first file supplies the starting value
@@ -510,23 +584,39 @@ int gmm_estimator_combine(const void* const* data, const uint64_t* size, uint32_
             if (f.mix[m].dens != sum.mix[m].dens)
                 return fail(GMM_ERR_INVALID_ARGUMENT, where + "mixture " + std::to_string(m) + " differs (topology mismatch)");
         // VectorAccumulator::operator+=: sum = sum + other, weight = weight + other
-        for (size_t a = 0; a < f.means.size() + f.covs.size(); ++a) {
-            Accumulator&       dst = a < f.means.size() ? sum.means[a] : sum.covs[a - f.means.size()];
-            const Accumulator& src = a < f.means.size() ? f.means[a] : f.covs[a - f.means.size()];
+        const auto add = [](Accumulator& dst, const Accumulator& src) {
             for (size_t k = 0; k < dst.sum.size(); ++k)
                 dst.sum[k] = dst.sum[k] + src.sum[k];
             dst.weight = dst.weight + src.weight;
-        }
-        for (size_t m = 0; m < f.mix.size(); ++m)
+        };
+        for (size_t a = 0; a < f.means.size(); ++a)
+            add(sum.means[a], f.means[a]);
+        for (size_t a = 0; a < f.covs.size(); ++a)
+            add(sum.covs[a], f.covs[a]);
+        // the denominator accumulators (EbwDiscriminativeMean/CovarianceEstimator::accumulate); none in an ML file
+        for (size_t a = 0; a < f.denMeans.size(); ++a)
+            add(sum.denMeans[a], f.denMeans[a]);
+        for (size_t a = 0; a < f.denCovs.size(); ++a)
+            add(sum.denCovs[a], f.denCovs[a]);
+        for (size_t m = 0; m < f.mix.size(); ++m) {
             for (size_t j = 0; j < f.mix[m].weights.size(); ++j)
                 sum.mix[m].weights[j] = sum.mix[m].weights[j] + f.mix[m].weights[j];
+            for (size_t j = 0; j < f.mix[m].denWeights.size(); ++j)  // weight += _weight, EbwDiscriminativeMixtureEstimator.cc:176-182
+                sum.mix[m].denWeights[j] = sum.mix[m].denWeights[j] + f.mix[m].denWeights[j];
+        }
+        sum.objective += f.objective;  // DiscriminativeMixtureSetEstimator.cc:168-174
     }
     Writer w;
     w.header(sum.dimension);
-    for (const std::vector<Accumulator>* accs : {&sum.means, &sum.covs}) {
-        w.put<uint32_t>(static_cast<uint32_t>(accs->size()));
-        for (const Accumulator& a : *accs)
-            w.accumulator(a.sum.data(), a.sum.size(), a.weight);
+    for (int which = 0; which < 2; ++which) {
+        const std::vector<Accumulator>& accs = which ? sum.covs : sum.means;
+        const std::vector<Accumulator>& den  = which ? sum.denCovs : sum.denMeans;
+        w.put<uint32_t>(static_cast<uint32_t>(accs.size()));
+        for (size_t i = 0; i < accs.size(); ++i) {
+            w.accumulator(accs[i].sum.data(), accs[i].sum.size(), accs[i].weight);
+            if (discriminative)
+                w.accumulator(den[i].sum.data(), den[i].sum.size(), den[i].weight);
+        }
     }
     w.put<uint32_t>(static_cast<uint32_t>(sum.dens.size()));
     for (const DensityEst& d : sum.dens) {
@@ -540,7 +630,11 @@ int gmm_estimator_combine(const void* const* data, const uint64_t* size, uint32_
             w.put<uint32_t>(x.dens[j]);
             w.put<double>(x.weights[j]);
         }
+        for (double dw : x.denWeights)
+            w.put<double>(dw);
     }
+    if (discriminative)
+        w.put<double>(sum.objective);
     *outSize = w.bytes.size();
     if (!out)
         return GMM_OK;
@@ -548,6 +642,367 @@ int gmm_estimator_combine(const void* const* data, const uint64_t* size, uint32_
         return fail(GMM_ERR_CAPACITY, "combine: " + std::to_string(w.bytes.size()) + " bytes, capacity " + std::to_string(capacity));
     std::memcpy(out, w.bytes.data(), w.bytes.size());
     return GMM_OK;
+}
+
+// ---- the EBW estimate (include/rasr_gmm_estimator.h, "The EBW estimate") ----
+
+void gmm_default_ebw_config(gmm_ebw_config* c) {
+    if (!c)
+        return;
+    c->minimum_observation_weight = 5.0;   // AbstractMixtureSetEstimator.cc:25-28
+    c->minimum_relative_weight    = 0.0;   // :30-33
+    c->minimum_variance           = 0.0;   // :35-38
+    c->normalize_mixture_weights  = 1;     // :55-58
+    c->iteration_constants_type   = GMM_EBW_GLOBAL_RWTH;  // IterationConstants.cc:659-663
+    c->step_size                  = 1.1;   // :665-673
+    c->minimum_icd                = 1.0;   // :675-678
+    c->beta                       = 1.0;   // :163-167
+    c->sigma_minimum              = -1.0;  // unset: sigma_minimum_factor * the smallest previous variance (:289-293)
+    c->sigma_minimum_factor       = 1e-5;  // :253-258
+    c->number_of_iterations       = 100;   // EbwDiscriminativeMixtureEstimator.cc:24-27
+}
+
+static int ebwEstimate(const void* data, uint64_t size, const gmm_mixture_set* prev, const gmm_ebw_config* config,
+                       gmm_mixture_set* out, std::vector<double>* constantsOut) {
+    if ((!data && size) || !prev)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null argument");
+    gmm_ebw_config cfg;
+    gmm_default_ebw_config(&cfg);
+    if (config)
+        cfg = *config;
+    if (cfg.iteration_constants_type == GMM_EBW_CAMBRIDGE)  // maximumRoot begins with require(false), IterationConstants.cc:595
+        return fail(GMM_ERR_UNSUPPORTED, "EBW estimate: iteration constants of type cambridge are not supported");
+    if (cfg.iteration_constants_type != GMM_EBW_GLOBAL_RWTH && cfg.iteration_constants_type != GMM_EBW_LOCAL_RWTH)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "EBW estimate: unknown iteration constants type");
+    EstimatorFile     f;
+    const std::string err = readEstimatorFile(data, size, f, true);
+    if (!err.empty())
+        return fail(GMM_ERR_INVALID_ARGUMENT, "EBW estimate: " + err);
+    // distributePreviousMixtureSet (DiscriminativeMixtureSetEstimator.cc:51-86): previous index i is file index i
+    const size_t D = f.dimension;
+    if (prev->dimension != f.dimension || prev->n_mixtures != f.mix.size() || prev->n_densities != f.dens.size() ||
+        prev->n_means != f.means.size() || prev->n_covariances != f.covs.size())
+        return fail(GMM_ERR_INVALID_ARGUMENT, "EBW estimate: previous mixture set differs in topology");
+    std::vector<std::vector<double>> prevW(f.mix.size());
+    for (size_t m = 0; m < f.mix.size(); ++m) {
+        const uint32_t e0 = prev->mixture_offsets[m], n = prev->mixture_offsets[m + 1] - e0;
+        if (n != f.mix[m].dens.size())  // setPreviousMixture: require(mixture->nDensities() == nDensities())
+            return fail(GMM_ERR_INVALID_ARGUMENT, "EBW estimate: previous mixture set differs in topology (mixture " +
+                                                          std::to_string(m) + ")");
+        for (uint32_t j = 0; j < n; ++j)
+            prevW[m].push_back(std::exp(prev->mixture_log_weights[e0 + j]));  // Mixture::weight
+    }
+    // removeDensitiesWithLowWeight (cc:136-140; DiscriminativeMixtureEstimator.cc:34-49, the unconditional --densityMax
+    // included)
+    if (cfg.minimum_observation_weight != 0 || cfg.minimum_relative_weight != 0)
+        for (size_t m = 0; m < f.mix.size(); ++m) {
+            MixtureEst& x = f.mix[m];
+            if (x.dens.empty())
+                return fail(GMM_ERR_INVALID_ARGUMENT, "EBW estimate: mixture " + std::to_string(m) + " has no densities");
+            uint32_t densityMax = 0;
+            for (uint32_t j = 1; j < x.dens.size(); ++j)
+                if (x.weights[j] > x.weights[densityMax])
+                    densityMax = j;
+            for (uint32_t j = 0; j < x.dens.size();) {
+                const bool enough = x.weights[j] >= cfg.minimum_observation_weight;
+                const bool enoughRelative = prevW[m][j] >= cfg.minimum_relative_weight;
+                if ((!enough || !enoughRelative) && j != densityMax) {
+                    x.dens.erase(x.dens.begin() + j);
+                    x.weights.erase(x.weights.begin() + j);
+                    x.denWeights.erase(x.denWeights.begin() + j);
+                    prevW[m].erase(prevW[m].begin() + j);
+                    --densityMax;
+                }
+                else
+                    ++j;
+            }
+        }
+    // MixtureSetEstimatorIndexMap after the removal; the densities of every covariance in (mixture, density) order
+    IndexMap meanMap(f.means.size()), covMap(f.covs.size()), densMap(f.dens.size());
+    struct Aug {
+        uint32_t dens, mix;
+        double   prevWeight;
+    };
+    std::vector<std::vector<Aug>> cim(f.covs.size());
+    std::vector<char>             seen(f.dens.size(), 0);
+    for (size_t m = 0; m < f.mix.size(); ++m)
+        for (size_t j = 0; j < f.mix[m].dens.size(); ++j) {
+            const uint32_t d = f.mix[m].dens[j];
+            if (seen[d])  // require(set.find(augmented) == set.end()), IterationConstants.cc:127
+                return fail(GMM_ERR_UNSUPPORTED, "EBW estimate: density " + std::to_string(d) + " is shared by more than one mixture entry");
+            seen[d] = 1;
+            meanMap.add(f.dens[d].mean);
+            covMap.add(f.dens[d].cov);
+            densMap.add(d);
+            cim[f.dens[d].cov].push_back(Aug{d, static_cast<uint32_t>(m), prevW[m][j]});
+        }
+    const auto dtW = [&](uint32_t mean) { return f.means[mean].weight - f.denMeans[mean].weight; };
+    // Xi (IterationConstants.cc:169-200)
+    std::vector<double> xi(f.mix.size());
+    for (size_t m = 0; m < f.mix.size(); ++m) {
+        double maxAbs = 0, maxNumDen = 0;
+        for (uint32_t d : f.mix[m].dens) {
+            const uint32_t mean = f.dens[d].mean;
+            const double   w = dtW(mean), a = std::fabs(w), den = f.denMeans[mean].weight;
+            if (maxAbs < a) {
+                maxAbs    = a;
+                maxNumDen = std::max(w + den, den);
+            }
+        }
+        const double denominator = (maxAbs < maxNumDen && maxNumDen > 0) ? 1 + (maxAbs - 1) * maxAbs / maxNumDen : 1;
+        xi[m]                    = cfg.beta / denominator;
+    }
+    // sigma-minimum (cc:271-293): over the covariances that hold a density
+    float minPrev = std::numeric_limits<float>::max();
+    for (uint32_t c : covMap.order)
+        for (size_t k = 0; k < D; ++k)
+            minPrev = std::min(minPrev, prev->variances[c * D + k]);
+    const double sigmaMin = cfg.sigma_minimum >= 0 ? cfg.sigma_minimum : cfg.sigma_minimum_factor * minPrev;
+    // the iteration constants b and the densities' constants, covariances in ascending OUTPUT index
+    std::vector<double> icMean(f.means.size(), 1.0);  // iterationConstant_(1)
+    std::vector<double> localB(f.mix.size(), 0.0);
+    std::vector<char>   localSet(f.mix.size(), 0);
+    std::vector<double> globalB(f.covs.size(), 0.0);
+    for (uint32_t c : covMap.order) {
+        // minimumDk (cc:298-334)
+        std::vector<double> numerator(D), denominator(D, 0.0);
+        for (size_t k = 0; k < D; ++k)
+            numerator[k] = 0 - (f.covs[c].sum[k] - f.denCovs[c].sum[k]);
+        for (const Aug& a : cim[c]) {
+            const uint32_t mean = f.dens[a.dens].mean;
+            const double   w    = dtW(mean);
+            for (size_t k = 0; k < D; ++k) {
+                const double dtSum = f.means[mean].sum[k] - f.denMeans[mean].sum[k];
+                const float  pm    = prev->means[mean * D + k];
+                const double t2    = 2 * dtSum - w * pm;
+                const double t3    = dtSum - w * pm;
+                numerator[k] += sigmaMin * w;
+                numerator[k] += t2 * pm;
+                numerator[k] += xi[a.mix] * t3 * t3;
+                denominator[k] += (prev->variances[c * D + k] - sigmaMin) * a.prevWeight;
+            }
+        }
+        double ratioMax = numerator[0] / denominator[0];
+        for (size_t k = 1; k < D; ++k) {
+            const double r = numerator[k] / denominator[k];
+            if (ratioMax < r)
+                ratioMax = r;
+        }
+        const double dkMin = ratioMax > 0 ? ratioMax : 0;
+        double       ic    = 1;  // Icb::default_
+        for (const Aug& a : cim[c]) {
+            double dk = 1 / xi[a.mix];
+            dk -= dtW(f.dens[a.dens].mean);
+            if (a.prevWeight > 0)
+                dk /= a.prevWeight;
+            if (cfg.iteration_constants_type == GMM_EBW_GLOBAL_RWTH)  // cc:371-383
+                ic = std::max(ic, std::max(dk, dkMin));
+            else {  // cc:425-437
+                if (!localSet[a.mix]) {
+                    localSet[a.mix] = 1;
+                    localB[a.mix]   = cfg.step_size * std::max(1.0, dkMin);
+                }
+                localB[a.mix] = std::max(cfg.step_size * dk, localB[a.mix]);
+            }
+        }
+        globalB[c] = ic * cfg.step_size;
+    }
+    for (uint32_t c : covMap.order)  // IterationConstants::set (cc:701-714), GlobalRwth / LocalRwth ::set
+        for (const Aug& a : cim[c]) {
+            double ic = cfg.iteration_constants_type == GMM_EBW_GLOBAL_RWTH ? globalB[c] : localB[a.mix];
+            ic *= a.prevWeight;  // usePooledVariances_
+            ic = std::max(cfg.minimum_icd, ic);
+            if (!(ic >= 0) || !std::isfinite(ic))  // setIterationConstant's verifies
+                return fail(GMM_ERR_INVALID_ARGUMENT, "EBW estimate: iteration constant of density " + std::to_string(a.dens) + " is not a finite non-negative number");
+            icMean[f.dens[a.dens].mean] = ic;
+        }
+    if (constantsOut) {
+        constantsOut->clear();
+        for (uint32_t d : densMap.order)
+            constantsOut->push_back(icMean[f.dens[d].mean]);
+    }
+    if (!out)
+        return GMM_OK;
+    std::memset(out, 0, sizeof(*out));
+    // mixture weights, the Cambridge scheme (EbwDiscriminativeMixtureEstimator.cc:39-91, 123-136)
+    std::vector<uint32_t> mixOff{0}, mixDens;
+    std::vector<double>   mixLogW;
+    for (size_t m = 0; m < f.mix.size(); ++m) {
+        const MixtureEst&   x = f.mix[m];
+        const size_t        n = x.dens.size();
+        std::vector<double> w;
+        if (n > 1 && x.weight() > 2.2204460492503131e-16) {
+            w.resize(n);
+            double kMax = 0;
+            for (size_t j = 0; j < n; ++j) {
+                w[j] = prevW[m][j];
+                if (w[j] > 2.2204460492503131e-16)
+                    kMax = std::max(kMax, x.denWeights[j] / w[j]);
+                else
+                    w[j] = 0;
+            }
+            std::vector<double> k(n, 0.0);
+            for (size_t j = 0; j < n; ++j)
+                if (w[j] > 0)
+                    k[j] = kMax - x.denWeights[j] / w[j];
+            for (uint32_t iter = 0; iter < cfg.number_of_iterations; ++iter) {
+                for (size_t j = 0; j < n; ++j) {
+                    if (w[j] > 0)
+                        w[j] = x.weights[j] + k[j] * w[j];
+                    if (w[j] < 0)
+                        w[j] = 0;
+                }
+                if (cfg.normalize_mixture_weights) {
+                    double sum = 0;
+                    for (double v : w)
+                        sum += v;
+                    if (sum > 2.2250738585072014e-308)
+                        for (double& v : w)
+                            v = v / sum;
+                    else
+                        for (double& v : w)
+                            v = 1 / static_cast<double>(n);
+                }
+            }
+        }
+        else
+            w.assign(n, cfg.normalize_mixture_weights ? 1 / static_cast<double>(n) : 1);
+        std::vector<double> lw;
+        for (size_t j = 0; j < n; ++j) {
+            mixDens.push_back(static_cast<uint32_t>(densMap.index[x.dens[j]]));
+            lw.push_back(w[j] > 0 ? std::log(w[j]) : -std::numeric_limits<double>::max());  // Mixture::addDensity
+        }
+        if (cfg.normalize_mixture_weights && !lw.empty()) {  // Mixture::normalizeWeights, logExpNorm
+            size_t maxIt = 0;
+            for (size_t j = 1; j < lw.size(); ++j)
+                if (lw[maxIt] < lw[j])
+                    maxIt = j;
+            double result = 0;
+            for (size_t j = 0; j < lw.size(); ++j)
+                if (j != maxIt)
+                    result += std::exp(lw[j] - lw[maxIt]);
+            const double logNorm = std::log1p(result) + lw[maxIt];
+            for (double& v : lw)
+                v = v - logNorm;
+        }
+        mixLogW.insert(mixLogW.end(), lw.begin(), lw.end());
+        mixOff.push_back(static_cast<uint32_t>(mixDens.size()));
+    }
+    std::vector<uint32_t> dnsMean, dnsCov;
+    for (uint32_t d : densMap.order) {
+        dnsMean.push_back(static_cast<uint32_t>(meanMap.index[f.dens[d].mean]));
+        dnsCov.push_back(static_cast<uint32_t>(covMap.index[f.dens[d].cov]));
+    }
+    // means (EbwDiscriminativeGaussDensityEstimator.cc:73-89), by file index: the covariances need them too
+    std::vector<float> newMean(f.means.size() * D);
+    for (size_t mean = 0; mean < f.means.size(); ++mean) {
+        const double ic = icMean[mean], weight = dtW(static_cast<uint32_t>(mean)) + ic;
+        for (size_t k = 0; k < D; ++k) {
+            const float pm = prev->means[mean * D + k];
+            if (weight > 0) {
+                const double buffer = (f.means[mean].sum[k] - f.denMeans[mean].sum[k]) + ic * pm;
+                newMean[mean * D + k] = static_cast<float>(buffer / weight);
+            }
+            else
+                newMean[mean * D + k] = pm;
+        }
+    }
+    std::vector<float> meanOut(meanMap.order.size() * D), varOut(covMap.order.size() * D);
+    for (size_t i = 0; i < meanMap.order.size(); ++i)
+        std::memcpy(&meanOut[i * D], &newMean[meanMap.order[i] * D], D * sizeof(float));
+    // covariances (cc:165-198): a covariance's means in order of first appearance among its densities
+    const float minVariance = static_cast<float>(cfg.minimum_variance);
+    for (size_t i = 0; i < covMap.order.size(); ++i) {
+        const uint32_t      c = covMap.order[i];
+        std::vector<double> buffer(D);
+        for (size_t k = 0; k < D; ++k)
+            buffer[k] = f.covs[c].sum[k] - f.denCovs[c].sum[k];
+        double            weight = 0;
+        std::vector<char> done(f.means.size(), 0);
+        for (const Aug& a : cim[c]) {
+            const uint32_t mean = f.dens[a.dens].mean;
+            if (done[mean])
+                continue;
+            done[mean]         = 1;
+            const double ic    = icMean[mean];
+            const double tmpW  = dtW(mean) + ic;
+            weight += tmpW;
+            for (size_t k = 0; k < D; ++k) {
+                const float pm          = prev->means[mean * D + k];
+                double      previousSum = prev->variances[c * D + k];
+                previousSum += pm * pm;  // an f32 product
+                previousSum *= ic;
+                const double newSum = tmpW * newMean[mean * D + k] * newMean[mean * D + k];
+                buffer[k] += previousSum - newSum;
+            }
+        }
+        if (!(weight > 0))  // verify(weight > 0)
+            return fail(GMM_ERR_INVALID_ARGUMENT, "EBW estimate: covariance " + std::to_string(c) + " has weight " + std::to_string(weight));
+        for (size_t k = 0; k < D; ++k) {
+            float v = static_cast<float>(buffer[k] / weight);
+            if (!(v > 0))  // verify(result->isPositiveDefinite())
+                return fail(GMM_ERR_INVALID_ARGUMENT, "EBW estimate: covariance " + std::to_string(c) + " component " +
+                                                              std::to_string(k) + " is not positive (" + std::to_string(v) + ")");
+            if (minVariance != 0 && v < minVariance)
+                v = minVariance;
+            varOut[i * D + k] = v;
+        }
+    }
+    gmm_mixture_set res;
+    res.dimension           = f.dimension;
+    res.n_means             = static_cast<uint32_t>(meanMap.order.size());
+    res.means               = copyOut(meanOut);
+    res.n_covariances       = static_cast<uint32_t>(covMap.order.size());
+    res.variances           = copyOut(varOut);
+    res.n_densities         = static_cast<uint32_t>(densMap.order.size());
+    res.density_mean        = copyOut(dnsMean);
+    res.density_covariance  = copyOut(dnsCov);
+    res.n_mixtures          = static_cast<uint32_t>(f.mix.size());
+    res.mixture_offsets     = copyOut(mixOff);
+    res.mixture_densities   = copyOut(mixDens);
+    res.mixture_log_weights = copyOut(mixLogW);
+    *out                    = res;
+    if (!res.means || !res.variances || !res.density_mean || !res.density_covariance || !res.mixture_offsets ||
+        !res.mixture_densities || !res.mixture_log_weights) {
+        gmm_mixture_set_free(out);
+        return fail(GMM_ERR_OUT_OF_MEMORY, "out of host memory");
+    }
+    return GMM_OK;
+}
+
+int gmm_estimator_estimate_ebw(const void* data, uint64_t size, const gmm_mixture_set* previous,
+                               const gmm_ebw_config* config, gmm_mixture_set* out) {
+    if (!out)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null argument");
+    return ebwEstimate(data, size, previous, config, out, nullptr);
+}
+
+int gmm_estimator_ebw_iteration_constants(const void* data, uint64_t size, const gmm_mixture_set* previous,
+                                          const gmm_ebw_config* config, double* constants, uint32_t capacity,
+                                          uint32_t* n) {
+    if (!n)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<double> ic;
+    const int           rc = ebwEstimate(data, size, previous, config, nullptr, &ic);
+    if (rc != GMM_OK)
+        return rc;
+    *n = static_cast<uint32_t>(ic.size());
+    if (!constants)
+        return GMM_OK;
+    if (capacity < ic.size())
+        return fail(GMM_ERR_CAPACITY, "EBW iteration constants: " + std::to_string(ic.size()) + " densities, capacity " + std::to_string(capacity));
+    std::memcpy(constants, ic.data(), ic.size() * sizeof(double));
+    return GMM_OK;
+}
+
+int gmm_estimator_combine(const void* const* data, const uint64_t* size, uint32_t n, void* out, uint64_t capacity,
+                          uint64_t* outSize) {
+    return combineFiles(data, size, n, out, capacity, outSize, false);
+}
+
+int gmm_estimator_combine_discriminative(const void* const* data, const uint64_t* size, uint32_t n, void* out,
+                                         uint64_t capacity, uint64_t* outSize) {
+    return combineFiles(data, size, n, out, capacity, outSize, true);
 }
 
 }  // extern "C"

@@ -4,6 +4,10 @@
 (AbstractMixtureSetEstimator::accumulate in Viterbi mode, or in Baum-Welch mode with the density posteriors of a
 diagonal-sum scorer), writes them as a RASR estimator file and estimates
 the next mixture set; `combine_estimators` adds several such files (the trainer's combine action, host only).
+
+For discriminative (EBW) training the same handle accumulates a pair's numerator and denominator weight in ONE call
+(`accumulate_discriminative_*`), keeps the objective function, and writes and combines the discriminative
+estimator's files (`to_bytes_discriminative`, `combine_discriminative_estimators`).
 """
 from __future__ import annotations
 
@@ -148,6 +152,158 @@ class Estimator:
             _ptr(pf), _ptr(pm), _ptr(pw), n, thr)
         _capi.check(rc, "gmm_estimator_accumulate_posteriors_host")
 
+    # ---- discriminative training: numerator and denominator weights in one call ----
+
+    @staticmethod
+    def _check_device_pairs(frames, pair_frame, lists, weights):
+        import torch
+        n = int(pair_frame.numel())
+        if frames.dtype != torch.float32 or frames.dim() != 2 or frames.stride(1) != 1:
+            raise ValueError("frames must be a float32 [F, >= D] tensor with unit column stride")
+        for name, t in lists:
+            if t is not None and (t.numel() != n or t.element_size() != 4 or t.dtype.is_floating_point
+                                  or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous int32 / uint32 tensor of n_pairs entries")
+        for name, t in weights:
+            if t is not None and (t.numel() != n or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float64 tensor of n_pairs entries")
+        return n
+
+    def accumulate_discriminative_device(self, frames, pair_frame, pair_mixture, pair_density=None, pair_weight_num=None,
+                                         pair_weight_den=None, scorer=None, stream=None, n_frames=None) -> None:
+        """gmm_estimator_accumulate_discriminative_device (Viterbi mode): accumulate_device with a numerator and a
+        denominator weight per pair (float64 cuda tensors).  A side given as None receives nothing (both None is an
+        error); a NaN weight marks the pair as absent on that side."""
+        import torch
+        f = int(frames.shape[0] if n_frames is None else n_frames)
+        n = self._check_device_pairs(
+            frames, pair_frame,
+            (("pair_frame", pair_frame), ("pair_mixture", pair_mixture), ("pair_density", pair_density)),
+            (("pair_weight_num", pair_weight_num), ("pair_weight_den", pair_weight_den)))
+        if stream is None:
+            stream = torch.cuda.current_stream(frames.device)
+        s = getattr(stream, "cuda_stream", stream)
+
+        def p(t):
+            return None if t is None else ctypes.c_void_p(t.data_ptr())
+        rc = self._lib.gmm_estimator_accumulate_discriminative_device(
+            self._h, scorer.handle if scorer is not None else None, p(frames), f, int(frames.stride(0)), p(pair_frame),
+            p(pair_mixture), p(pair_density), p(pair_weight_num), p(pair_weight_den), n,
+            ctypes.c_void_p(s) if s else None)
+        _capi.check(rc, "gmm_estimator_accumulate_discriminative_device")
+
+    def accumulate_discriminative_host(self, frames, pair_frame, pair_mixture, pair_density=None, pair_weight_num=None,
+                                       pair_weight_den=None, scorer=None) -> None:
+        """gmm_estimator_accumulate_discriminative_host: the same call on numpy arrays, synchronous."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        if frames.ndim != 2:
+            raise ValueError("frames must be [F, >= D]")
+        pf = np.ascontiguousarray(pair_frame, dtype=np.uint32)
+        pm = np.ascontiguousarray(pair_mixture, dtype=np.uint32)
+        pd = None if pair_density is None else np.ascontiguousarray(pair_density, dtype=np.uint32)
+        wn = None if pair_weight_num is None else np.ascontiguousarray(pair_weight_num, dtype=np.float64)
+        wd = None if pair_weight_den is None else np.ascontiguousarray(pair_weight_den, dtype=np.float64)
+        n = pf.shape[0]
+        if pf.ndim != 1 or any(a is not None and a.shape != (n,) for a in (pm, pd, wn, wd)):
+            raise ValueError("the pair arrays must be 1-d arrays of one length")
+        rc = self._lib.gmm_estimator_accumulate_discriminative_host(
+            self._h, scorer.handle if scorer is not None else None, _ptr(frames), frames.shape[0], frames.shape[1],
+            _ptr(pf), _ptr(pm), _ptr(pd), _ptr(wn), _ptr(wd), n)
+        _capi.check(rc, "gmm_estimator_accumulate_discriminative_host")
+
+    def accumulate_discriminative_posteriors_device(self, frames, pair_frame, pair_mixture, pair_weight_num=None,
+                                                    pair_weight_den=None, scorer=None, weight_threshold=None,
+                                                    stream=None, n_frames=None) -> None:
+        """gmm_estimator_accumulate_discriminative_posteriors_device (Baum-Welch mode): the density posteriors of
+        `scorer` are computed once per pair; a contribution is live on a side iff that side's pair weight * posterior
+        > weight_threshold.  Tensors as accumulate_discriminative_device."""
+        import torch
+        f = int(frames.shape[0] if n_frames is None else n_frames)
+        n = self._check_device_pairs(
+            frames, pair_frame, (("pair_frame", pair_frame), ("pair_mixture", pair_mixture)),
+            (("pair_weight_num", pair_weight_num), ("pair_weight_den", pair_weight_den)))
+        if stream is None:
+            stream = torch.cuda.current_stream(frames.device)
+        s = getattr(stream, "cuda_stream", stream)
+        thr = _capi.DEFAULT_WEIGHT_THRESHOLD if weight_threshold is None else float(weight_threshold)
+
+        def p(t):
+            return None if t is None else ctypes.c_void_p(t.data_ptr())
+        rc = self._lib.gmm_estimator_accumulate_discriminative_posteriors_device(
+            self._h, scorer.handle if scorer is not None else None, p(frames), f, int(frames.stride(0)), p(pair_frame),
+            p(pair_mixture), p(pair_weight_num), p(pair_weight_den), n, thr, ctypes.c_void_p(s) if s else None)
+        _capi.check(rc, "gmm_estimator_accumulate_discriminative_posteriors_device")
+
+    def accumulate_discriminative_posteriors_host(self, frames, pair_frame, pair_mixture, pair_weight_num=None,
+                                                  pair_weight_den=None, scorer=None, weight_threshold=None) -> None:
+        """gmm_estimator_accumulate_discriminative_posteriors_host: the same call on numpy arrays, synchronous."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        if frames.ndim != 2:
+            raise ValueError("frames must be [F, >= D]")
+        pf = np.ascontiguousarray(pair_frame, dtype=np.uint32)
+        pm = np.ascontiguousarray(pair_mixture, dtype=np.uint32)
+        wn = None if pair_weight_num is None else np.ascontiguousarray(pair_weight_num, dtype=np.float64)
+        wd = None if pair_weight_den is None else np.ascontiguousarray(pair_weight_den, dtype=np.float64)
+        n = pf.shape[0]
+        if pf.ndim != 1 or any(a is not None and a.shape != (n,) for a in (pm, wn, wd)):
+            raise ValueError("the pair arrays must be 1-d arrays of one length")
+        thr = _capi.DEFAULT_WEIGHT_THRESHOLD if weight_threshold is None else float(weight_threshold)
+        rc = self._lib.gmm_estimator_accumulate_discriminative_posteriors_host(
+            self._h, scorer.handle if scorer is not None else None, _ptr(frames), frames.shape[0], frames.shape[1],
+            _ptr(pf), _ptr(pm), _ptr(wn), _ptr(wd), n, thr)
+        _capi.check(rc, "gmm_estimator_accumulate_discriminative_posteriors_host")
+
+    def accumulate_objective(self, f: float) -> None:
+        """gmm_estimator_accumulate_objective: objective function += f (host)."""
+        _capi.check(self._lib.gmm_estimator_accumulate_objective(self._h, float(f)), "gmm_estimator_accumulate_objective")
+
+    @property
+    def objective(self) -> float:
+        v = ctypes.c_double()
+        _capi.check(self._lib.gmm_estimator_objective(self._h, ctypes.byref(v)), "gmm_estimator_objective")
+        return float(v.value)
+
+    def get_denominator(self) -> dict:
+        """The denominator tables, keys and shapes as get() (zeros before the first discriminative call)."""
+        t = self.topology
+        D = t.dimension
+        out = {"mean_sums": np.zeros((t.means.shape[0], D), np.float64),
+               "mean_weights": np.zeros(t.means.shape[0], np.float64),
+               "covariance_sums": np.zeros((t.n_covariances, D), np.float64),
+               "covariance_weights": np.zeros(t.n_covariances, np.float64),
+               "entry_weights": np.zeros(t.n_entries, np.float64)}
+        _capi.check(self._lib.gmm_estimator_get_denominator(
+            self._h, _ptr(out["mean_sums"]), _ptr(out["mean_weights"]), _ptr(out["covariance_sums"]),
+            _ptr(out["covariance_weights"]), _ptr(out["entry_weights"])), "gmm_estimator_get_denominator")
+        return out
+
+    def to_bytes_discriminative(self) -> bytes:
+        """gmm_estimator_serialize_discriminative: the file the discriminative (EBW) estimator's write produces."""
+        size = ctypes.c_uint64()
+        _capi.check(self._lib.gmm_estimator_serialize_discriminative(self._h, None, 0, ctypes.byref(size)),
+                    "gmm_estimator_serialize_discriminative")
+        buf = ctypes.create_string_buffer(max(int(size.value), 1))
+        _capi.check(self._lib.gmm_estimator_serialize_discriminative(self._h, buf, size.value, ctypes.byref(size)),
+                    "gmm_estimator_serialize_discriminative")
+        return buf.raw[:size.value]
+
+    def write_discriminative(self, path) -> None:
+        _capi.check(self._lib.gmm_estimator_write_discriminative(self._h, os.fsencode(path)),
+                    "gmm_estimator_write_discriminative")
+
+    def estimate_ebw(self, previous: MixtureSet, **config) -> MixtureSet:
+        """gmm_estimator_estimate_ebw_handle: the EBW estimate from the numerator and denominator tables and the
+        previous mixture set (keywords: ebw_config)."""
+        d = _capi.MixtureSetDesc()
+        cfg = ebw_config(**config)
+        prev = previous.desc()
+        _capi.check(self._lib.gmm_estimator_estimate_ebw_handle(self._h, ctypes.byref(prev), ctypes.byref(cfg),
+                                                                ctypes.byref(d)), "gmm_estimator_estimate_ebw_handle")
+        try:
+            return _from_desc(d)
+        finally:
+            self._lib.gmm_mixture_set_free(ctypes.byref(d))
+
     @property
     def skipped(self) -> int:
         """Pairs skipped since creation or the last reset (out-of-range frame, mixture or density, no best density)."""
@@ -193,16 +349,67 @@ class Estimator:
             self._lib.gmm_mixture_set_free(ctypes.byref(d))
 
 
+def ebw_config(**kw) -> _capi.EbwConfig:
+    """gmm_ebw_config with the reference defaults, overridden by keyword (the struct's fields;
+    iteration_constants_type as "global-rwth" / "local-rwth" / "cambridge")."""
+    cfg = _capi.EbwConfig()
+    _capi.load_library().gmm_default_ebw_config(ctypes.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise TypeError(f"unknown EBW parameter {k}")
+        setattr(cfg, k, _capi.EBW_TYPES[v] if k == "iteration_constants_type" else v)
+    return cfg
+
+
+def estimate_ebw(data: bytes, previous: MixtureSet, **config) -> MixtureSet:
+    """gmm_estimator_estimate_ebw: the EBW estimate from a discriminative estimator file's bytes (host only)."""
+    lib = _capi.load_library()
+    d = _capi.MixtureSetDesc()
+    cfg, prev = ebw_config(**config), previous.desc()
+    buf = ctypes.create_string_buffer(data, max(len(data), 1))
+    _capi.check(lib.gmm_estimator_estimate_ebw(buf, len(data), ctypes.byref(prev), ctypes.byref(cfg), ctypes.byref(d)),
+                "gmm_estimator_estimate_ebw")
+    try:
+        return _from_desc(d)
+    finally:
+        lib.gmm_mixture_set_free(ctypes.byref(d))
+
+
+def ebw_iteration_constants(data: bytes, previous: MixtureSet, **config) -> np.ndarray:
+    """gmm_estimator_ebw_iteration_constants: the f64 iteration constant of every density of the estimated set."""
+    lib = _capi.load_library()
+    cfg, prev = ebw_config(**config), previous.desc()
+    buf = ctypes.create_string_buffer(data, max(len(data), 1))
+    n = ctypes.c_uint32()
+    _capi.check(lib.gmm_estimator_ebw_iteration_constants(buf, len(data), ctypes.byref(prev), ctypes.byref(cfg), None, 0,
+                                                          ctypes.byref(n)), "gmm_estimator_ebw_iteration_constants")
+    out = np.zeros(n.value, np.float64)
+    _capi.check(lib.gmm_estimator_ebw_iteration_constants(buf, len(data), ctypes.byref(prev), ctypes.byref(cfg), _ptr(out),
+                                                          n.value, ctypes.byref(n)), "gmm_estimator_ebw_iteration_constants")
+    return out
+
+
+def combine_discriminative_estimators(files) -> bytes:
+    """gmm_estimator_combine_discriminative: combine_estimators for discriminative estimator files (the denominator
+    accumulators, the denominator weights and the objective functions are added in file order too)."""
+    return _combine(files, "gmm_estimator_combine_discriminative")
+
+
 def combine_estimators(files) -> bytes:
     """gmm_estimator_combine: the bytes of several estimator files of one topology added in order (host only)."""
+    return _combine(files, "gmm_estimator_combine")
+
+
+def _combine(files, name) -> bytes:
     lib = _capi.load_library()
+    fn = getattr(lib, name)
     files = [bytes(f) for f in files]
     n = len(files)
     bufs = [ctypes.create_string_buffer(f, max(len(f), 1)) for f in files]
     data = (ctypes.c_void_p * max(n, 1))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
     sizes = (ctypes.c_uint64 * max(n, 1))(*[len(f) for f in files])
     size = ctypes.c_uint64()
-    _capi.check(lib.gmm_estimator_combine(data, sizes, n, None, 0, ctypes.byref(size)), "gmm_estimator_combine")
+    _capi.check(fn(data, sizes, n, None, 0, ctypes.byref(size)), name)
     out = ctypes.create_string_buffer(max(int(size.value), 1))
-    _capi.check(lib.gmm_estimator_combine(data, sizes, n, out, size.value, ctypes.byref(size)), "gmm_estimator_combine")
+    _capi.check(fn(data, sizes, n, out, size.value, ctypes.byref(size)), name)
     return out.raw[:size.value]
