@@ -28,11 +28,14 @@ OBJS      = $(BUILD)/gmm_kernels_i8.o $(BUILD)/gmm_kernels_f32.o $(BUILD)/gmm_ke
             $(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o \
             $(BUILD)/gmm_kernels_accum.o $(BUILD)/gmm_kernels_accum_dual.o $(BUILD)/gmm_estimator.o $(BUILD)/gmm_kernels_posterior.o \
             $(BUILD)/gmm_kernels_state.o $(BUILD)/gmm_state.o \
-            $(BUILD)/gmm_kernels_adapt.o $(BUILD)/gmm_adapt.o $(BUILD)/AffineTransformEstimate.o
+            $(BUILD)/gmm_kernels_adapt.o $(BUILD)/gmm_adapt.o $(BUILD)/AffineTransformEstimate.o \
+            $(BUILD)/gmm_kernels_mllr.o $(BUILD)/gmm_mllr.o $(BUILD)/MllrEstimate.o
 # include/rasr_gmm_estimator.h: the units behind it depend on these besides HDRS
 EST_HDRS  = include/rasr_gmm_estimator.h $(SRC)/gmm_estimator.hh
 # include/rasr_gmm_adaptation.h: the units behind it depend on these besides HDRS
 ADAPT_HDRS = include/rasr_gmm_adaptation.h $(SRC)/gmm_adapt.hh
+# include/rasr_gmm_mllr.h: the units behind it depend on these besides HDRS (pass 3 is the affine index pass)
+MLLR_HDRS = include/rasr_gmm_mllr.h $(SRC)/gmm_mllr.hh $(ADAPT_HDRS)
 DRIVER    = $(BUILD)/tests/feature_scorer_driver
 
 REFSORT   = $(BUILD)/tests/refsort_test
@@ -40,8 +43,9 @@ CLASSLAYOUT = $(BUILD)/tests/class_layout_test
 ESTCOMBINE = $(BUILD)/tests/estimator_combine_test
 AFFINEEST = $(BUILD)/tests/affine_estimate_test
 EBWEST   = $(BUILD)/tests/ebw_estimate_test
+MLLREST  = $(BUILD)/tests/mllr_estimate_test
 
-all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) $(EBWEST) oracle check-integration
+all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) $(EBWEST) $(MLLREST) oracle check-integration
 
 $(BUILD)/gmm_kernels_i8.o: $(SRC)/gmm_kernels_i8.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -110,6 +114,20 @@ $(BUILD)/gmm_adapt.o: $(SRC)/gmm_adapt.cc $(HDRS) $(EST_HDRS) $(ADAPT_HDRS)
 	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
 
 $(BUILD)/AffineTransformEstimate.o: $(SRC)/host/AffineTransformEstimate.cc include/rasr_gmm.h include/rasr_gmm_adaptation.h
+	@mkdir -p $(BUILD)
+	g++ $(HOSTFLAGS) -c $< -o $@
+
+# MLLR mean transform accumulation per (speaker key, regression leaf) (gmm_mllr_accumulate_*): resolve, one sort by
+# set, ordered f64 sums; gmm_kernels_adapt's flags.  Not one of KERNEL_OBJS
+$(BUILD)/gmm_kernels_mllr.o: $(SRC)/gmm_kernels_mllr.hip $(MLLR_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/gmm_mllr.o: $(SRC)/gmm_mllr.cc $(HDRS) $(EST_HDRS) $(MLLR_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
+
+$(BUILD)/MllrEstimate.o: $(SRC)/host/MllrEstimate.cc include/rasr_gmm.h include/rasr_gmm_mllr.h
 	@mkdir -p $(BUILD)
 	g++ $(HOSTFLAGS) -c $< -o $@
 
@@ -214,6 +232,11 @@ $(EBWEST): tests/cpp/ebw_estimate_test.cc $(SRC)/host/MixtureSetEstimatorFile.cc
 $(AFFINEEST): tests/cpp/affine_estimate_test.cc $(SRC)/host/AffineTransformEstimate.cc include/rasr_gmm.h include/rasr_gmm_adaptation.h
 	@mkdir -p $(BUILD)/tests
 	g++ $(HOSTFLAGS) $(AFFINEEST_FLAGS) -o $@ $< $(SRC)/host/AffineTransformEstimate.cc
+
+# host check of gmm_mllr_estimate and gmm_mllr_adapt_means (no GPU, no HIP): the estimate unit alone
+$(MLLREST): tests/cpp/mllr_estimate_test.cc $(SRC)/host/MllrEstimate.cc include/rasr_gmm.h include/rasr_gmm_mllr.h
+	@mkdir -p $(BUILD)/tests
+	g++ $(HOSTFLAGS) $(MLLREST_FLAGS) -o $@ $< $(SRC)/host/MllrEstimate.cc
 
 $(DRIVER): tests/cpp/feature_scorer_driver.cc $(LIB) $(HDRS)
 	@mkdir -p $(BUILD)/tests

@@ -11,7 +11,9 @@
  *   AffineFeatureTransformAccumulator::combine      src/Mm/AffineFeatureTransformAccumulator.cc:345-365
  * (driven per key by Speech::AffineFeatureTransformEstimator / KeyedEstimator).  Not covered: the hlda criterion and a
  * feature dimension other than the model dimension, score() and its log-determinant, the binary and XML accumulator
- * files (read / write / dump), applying a transform to frames, MLLR mean transforms and regression trees.
+ * files (read / write / dump), applying a transform to frames.  MLLR mean transforms over a regression tree are
+ * rasr_gmm_mllr.h; BandMllrAdaptation, SemiTiedAdaptation, the estimator and adaptor files, building the tree from a
+ * CART and a RASR-side adapter remain out.
  *
  * THE TABLES of one key, D the dimension of the mixture set (feature dimension = model dimension):
  *   beta                 the summed weight

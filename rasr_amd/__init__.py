@@ -10,6 +10,7 @@ from ._capi import (BATCH_DIAGONAL_MAXIMUM_FAST, BATCH_DIAGONAL_MAXIMUM_FLOAT, B
 from .adaptation import AffineTransformAccumulator, estimate_affine_transform
 from .estimator import (Estimator, combine_discriminative_estimators, combine_estimators, ebw_config,
                         ebw_iteration_constants, estimate_ebw)
+from .mllr import MLLR_KINDS, MllrAccumulator, adapt_means, estimate_mllr
 from .mixture_set import (MixtureSet, estimate_mixture_set, estimator_config, parse_mixture_set, ragged_counts,
                           read_mixture_set, synthetic_frames,
                           synthetic_mixture_set, write_mixture_set)
@@ -23,4 +24,5 @@ __all__ = [
     "Estimator", "combine_estimators", "combine_discriminative_estimators", "estimate_ebw", "ebw_iteration_constants",
     "ebw_config", "DEFAULT_WEIGHT_THRESHOLD", "STATE_POSTERIOR_CHUNK", "float_spread_bound",
     "AffineTransformAccumulator", "estimate_affine_transform",
+    "MLLR_KINDS", "MllrAccumulator", "estimate_mllr", "adapt_means",
 ]

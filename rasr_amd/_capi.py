@@ -21,6 +21,10 @@ GMM_ERR_OUT_OF_MEMORY = -4
 GMM_ERR_CAPACITY = -5
 GMM_ESTIMATOR_CHUNK = 512  # include/rasr_gmm_estimator.h: part of the accumulation's numeric contract
 GMM_AFFINE_CHUNK = 512  # include/rasr_gmm_adaptation.h: part of the affine accumulation's numeric contract
+GMM_MLLR_CHUNK = 512  # include/rasr_gmm_mllr.h: part of the MLLR accumulation's numeric contract
+GMM_MLLR_FULL = 1  # the kinds of MLLR statistics (a mask for gmm_mllr_create)
+GMM_MLLR_SHIFT = 2
+GMM_MLLR_NO_ID = 0xFFFFFFFF  # "none" in the tree arrays of gmm_mllr_estimate
 STATE_POSTERIOR_CHUNK = 256  # include/rasr_gmm.h GMM_STATE_POSTERIOR_CHUNK: part of the state posteriors' contract
 # GMM_ESTIMATOR_DEFAULT_WEIGHT_THRESHOLD: Core::Type<f32>::epsilon, the Baum-Welch weightThreshold_
 DEFAULT_WEIGHT_THRESHOLD = 2.0 ** -23
@@ -131,8 +135,8 @@ GMM_HOST_ASYNC = 8
 # gmm_scorer_create_sharded: the per-frame reduce of mixtures split between GPUs
 GMM_EXCHANGE = {"auto": 0, "rccl": 1, "copy": 2}
 
-# (name, restype, argtypes) for every function declared in include/rasr_gmm.h, rasr_gmm_io.h, rasr_gmm_estimator.h
-# and rasr_gmm_adaptation.h
+# (name, restype, argtypes) for every function declared in include/rasr_gmm.h, rasr_gmm_io.h, rasr_gmm_estimator.h,
+# rasr_gmm_adaptation.h and rasr_gmm_mllr.h
 PROTOTYPES = [
     ("gmm_default_config", None, [ctypes.POINTER(ScorerConfig)]),
     ("gmm_scorer_create", ctypes.c_int,
@@ -306,6 +310,35 @@ PROTOTYPES = [
     ("gmm_affine_estimate", ctypes.c_int,
      [ctypes.c_uint32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
       ctypes.c_uint32, ctypes.c_double, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    # include/rasr_gmm_mllr.h
+    ("gmm_mllr_create", ctypes.c_int,
+     [ctypes.POINTER(MixtureSetDesc), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
+      ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    ("gmm_mllr_destroy", ctypes.c_int, [ctypes.c_void_p]),
+    ("gmm_mllr_reset", ctypes.c_int, [ctypes.c_void_p]),
+    ("gmm_mllr_accumulate_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("gmm_mllr_accumulate_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    ("gmm_mllr_skipped", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
+    ("gmm_mllr_info", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]),
+    ("gmm_mllr_get", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("gmm_mllr_add", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double]),
+    ("gmm_mllr_estimate", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_double,
+      ctypes.c_double, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("gmm_mllr_adapt_means", ctypes.c_int,
+     [ctypes.POINTER(MixtureSetDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int,
+      ctypes.c_void_p]),
     ("gmm_version", ctypes.c_char_p, []),
     ("gmm_kernel_id", ctypes.c_char_p, []),
 ]
