@@ -28,14 +28,18 @@ OBJS      = $(BUILD)/gmm_kernels_i8.o $(BUILD)/gmm_kernels_f32.o $(BUILD)/gmm_ke
             $(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o \
             $(BUILD)/gmm_kernels_accum.o $(BUILD)/gmm_kernels_accum_dual.o $(BUILD)/gmm_estimator.o $(BUILD)/gmm_kernels_posterior.o \
             $(BUILD)/gmm_kernels_state.o $(BUILD)/gmm_state.o \
+            $(BUILD)/gmm_kernels_keyed.o $(BUILD)/gmm_pairaccum.o $(BUILD)/PairTopology.o \
             $(BUILD)/gmm_kernels_adapt.o $(BUILD)/gmm_adapt.o $(BUILD)/AffineTransformEstimate.o \
             $(BUILD)/gmm_kernels_mllr.o $(BUILD)/gmm_mllr.o $(BUILD)/MllrEstimate.o
+# the core of the handles that accumulate pairs (gmm_pairaccum.hh names the chunk constants of both adaptation headers)
+PAIR_HDRS = $(SRC)/gmm_pairaccum.hh $(SRC)/host/PairTopology.hh $(SRC)/gmm_estimator.hh include/rasr_gmm_estimator.h \
+            include/rasr_gmm_adaptation.h include/rasr_gmm_mllr.h
 # include/rasr_gmm_estimator.h: the units behind it depend on these besides HDRS
-EST_HDRS  = include/rasr_gmm_estimator.h $(SRC)/gmm_estimator.hh
+EST_HDRS  = $(PAIR_HDRS)
 # include/rasr_gmm_adaptation.h: the units behind it depend on these besides HDRS
-ADAPT_HDRS = include/rasr_gmm_adaptation.h $(SRC)/gmm_adapt.hh
-# include/rasr_gmm_mllr.h: the units behind it depend on these besides HDRS (pass 3 is the affine index pass)
-MLLR_HDRS = include/rasr_gmm_mllr.h $(SRC)/gmm_mllr.hh $(ADAPT_HDRS)
+ADAPT_HDRS = $(PAIR_HDRS) $(SRC)/gmm_adapt.hh
+# include/rasr_gmm_mllr.h: the units behind it depend on these besides HDRS
+MLLR_HDRS = $(PAIR_HDRS) $(SRC)/gmm_mllr.hh
 DRIVER    = $(BUILD)/tests/feature_scorer_driver
 
 REFSORT   = $(BUILD)/tests/refsort_test
@@ -44,8 +48,9 @@ ESTCOMBINE = $(BUILD)/tests/estimator_combine_test
 AFFINEEST = $(BUILD)/tests/affine_estimate_test
 EBWEST   = $(BUILD)/tests/ebw_estimate_test
 MLLREST  = $(BUILD)/tests/mllr_estimate_test
+PAIRTOPO = $(BUILD)/tests/pair_topology_test
 
-all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) $(EBWEST) $(MLLREST) oracle check-integration
+all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) $(EBWEST) $(MLLREST) $(PAIRTOPO) oracle check-integration
 
 $(BUILD)/gmm_kernels_i8.o: $(SRC)/gmm_kernels_i8.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -103,13 +108,27 @@ $(BUILD)/gmm_estimator.o: $(SRC)/gmm_estimator.cc $(HDRS) $(EST_HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
 
-# affine feature transform (CMLLR) accumulation per speaker key (gmm_affine_accumulate_*): resolve, one sort by key,
-# ordered f64 sums with a correctly rounded division per G term.  Not one of KERNEL_OBJS
-$(BUILD)/gmm_kernels_adapt.o: $(SRC)/gmm_kernels_adapt.hip $(ADAPT_HDRS)
+# the shared core (gmm_pairaccum.hh): checks, staging and call shapes of the estimator, affine and MLLR handles; the
+# keyed handles' resolve / index / combine passes, built with gmm_kernels_adapt's flags.  Not one of KERNEL_OBJS
+$(BUILD)/gmm_kernels_keyed.o: $(SRC)/gmm_kernels_keyed.hip $(HDRS) $(PAIR_HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BUILD)/gmm_adapt.o: $(SRC)/gmm_adapt.cc $(HDRS) $(EST_HDRS) $(ADAPT_HDRS)
+$(BUILD)/gmm_pairaccum.o: $(SRC)/gmm_pairaccum.cc $(HDRS) $(PAIR_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
+
+$(BUILD)/PairTopology.o: $(SRC)/host/PairTopology.cc $(SRC)/host/PairTopology.hh include/rasr_gmm.h
+	@mkdir -p $(BUILD)
+	g++ $(HOSTFLAGS) -c $< -o $@
+
+# affine feature transform (CMLLR) accumulation per speaker key (gmm_affine_accumulate_*): the pieces'
+# ordered f64 sums with a correctly rounded division per G term.  Not one of KERNEL_OBJS
+$(BUILD)/gmm_kernels_adapt.o: $(SRC)/gmm_kernels_adapt.hip $(HDRS) $(ADAPT_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/gmm_adapt.o: $(SRC)/gmm_adapt.cc $(HDRS) $(ADAPT_HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
 
@@ -117,13 +136,13 @@ $(BUILD)/AffineTransformEstimate.o: $(SRC)/host/AffineTransformEstimate.cc inclu
 	@mkdir -p $(BUILD)
 	g++ $(HOSTFLAGS) -c $< -o $@
 
-# MLLR mean transform accumulation per (speaker key, regression leaf) (gmm_mllr_accumulate_*): resolve, one sort by
-# set, ordered f64 sums; gmm_kernels_adapt's flags.  Not one of KERNEL_OBJS
-$(BUILD)/gmm_kernels_mllr.o: $(SRC)/gmm_kernels_mllr.hip $(MLLR_HDRS)
+# MLLR mean transform accumulation per (speaker key, regression leaf) (gmm_mllr_accumulate_*): the pieces'
+# ordered f64 sums; gmm_kernels_adapt's flags.  Not one of KERNEL_OBJS
+$(BUILD)/gmm_kernels_mllr.o: $(SRC)/gmm_kernels_mllr.hip $(HDRS) $(MLLR_HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(BUILD)/gmm_mllr.o: $(SRC)/gmm_mllr.cc $(HDRS) $(EST_HDRS) $(MLLR_HDRS)
+$(BUILD)/gmm_mllr.o: $(SRC)/gmm_mllr.cc $(HDRS) $(MLLR_HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
 
@@ -237,6 +256,11 @@ $(AFFINEEST): tests/cpp/affine_estimate_test.cc $(SRC)/host/AffineTransformEstim
 $(MLLREST): tests/cpp/mllr_estimate_test.cc $(SRC)/host/MllrEstimate.cc include/rasr_gmm.h include/rasr_gmm_mllr.h
 	@mkdir -p $(BUILD)/tests
 	g++ $(HOSTFLAGS) $(MLLREST_FLAGS) -o $@ $< $(SRC)/host/MllrEstimate.cc
+
+# host check of the topology validation and expansion that the three accumulating handles share (no GPU, no HIP)
+$(PAIRTOPO): tests/cpp/pair_topology_test.cc $(SRC)/host/PairTopology.cc $(SRC)/host/PairTopology.hh include/rasr_gmm.h
+	@mkdir -p $(BUILD)/tests
+	g++ $(HOSTFLAGS) $(PAIRTOPO_FLAGS) -o $@ $< $(SRC)/host/PairTopology.cc
 
 $(DRIVER): tests/cpp/feature_scorer_driver.cc $(LIB) $(HDRS)
 	@mkdir -p $(BUILD)/tests

@@ -10,14 +10,13 @@ import ctypes
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _pairs
 from .mixture_set import MixtureSet
 
 CRITERIA = {"naive": 0, "mmiPrime": 1, "hlda": 2}  # gmm_affine_criterion
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+_ptr = _pairs.ptr
 
 
 class AffineTransformAccumulator:
@@ -69,44 +68,20 @@ class AffineTransformAccumulator:
         pair_key int32 or uint32 cuda tensors of n_pairs; pair_weight a float64 cuda tensor or None (weight 1);
         pair_key None: key 0.  Without pair_density the density is the scorer's best density of the pair (`scorer`: a
         Scorer), or, without a scorer, the only density of the mixture.  Asynchronous on `stream`."""
-        import torch
         f = int(frames.shape[0] if n_frames is None else n_frames)
-        n = int(pair_frame.numel())
-        if frames.dtype != torch.float32 or frames.dim() != 2 or frames.stride(1) != 1:
-            raise ValueError("frames must be a float32 [F, >= D] tensor with unit column stride")
-        for name, t in (("pair_frame", pair_frame), ("pair_mixture", pair_mixture), ("pair_density", pair_density),
-                        ("pair_key", pair_key)):
-            if t is not None and (t.numel() != n or t.element_size() != 4 or t.dtype.is_floating_point
-                                  or not t.is_contiguous()):
-                raise ValueError(f"{name} must be a contiguous int32 / uint32 tensor of n_pairs entries")
-        if pair_weight is not None and (pair_weight.numel() != n or pair_weight.dtype != torch.float64
-                                        or not pair_weight.is_contiguous()):
-            raise ValueError("pair_weight must be a contiguous float64 tensor of n_pairs entries")
-        if stream is None:
-            stream = torch.cuda.current_stream(frames.device)
-        s = getattr(stream, "cuda_stream", stream)
-
-        def p(t):
-            return None if t is None else ctypes.c_void_p(t.data_ptr())
+        n, s, p = _pairs.device_pairs(
+            frames, (("pair_frame", pair_frame), ("pair_mixture", pair_mixture), ("pair_density", pair_density),
+                     ("pair_key", pair_key)), (("pair_weight", pair_weight),), stream)
         rc = self._lib.gmm_affine_accumulate_device(
-            self._h, scorer.handle if scorer is not None else None, p(frames), f, int(frames.stride(0)), p(pair_frame),
-            p(pair_mixture), p(pair_density), p(pair_weight), p(pair_key), n, ctypes.c_void_p(s) if s else None)
+            self._h, scorer.handle if scorer is not None else None, p[0], f, int(frames.stride(0)), p[1], p[2], p[3], p[5],
+            p[4], n, s)
         _capi.check(rc, "gmm_affine_accumulate_device")
 
     def accumulate(self, frames, pair_frame, pair_mixture, pair_density=None, pair_weight=None, pair_key=None,
                    scorer=None) -> None:
         """gmm_affine_accumulate_host: the same call on numpy arrays, synchronous."""
-        frames = np.ascontiguousarray(frames, dtype=np.float32)
-        if frames.ndim != 2:
-            raise ValueError("frames must be [F, >= D]")
-        pf = np.ascontiguousarray(pair_frame, dtype=np.uint32)
-        pm = np.ascontiguousarray(pair_mixture, dtype=np.uint32)
-        pd = None if pair_density is None else np.ascontiguousarray(pair_density, dtype=np.uint32)
-        pk = None if pair_key is None else np.ascontiguousarray(pair_key, dtype=np.uint32)
-        pw = None if pair_weight is None else np.ascontiguousarray(pair_weight, dtype=np.float64)
-        n = pf.shape[0]
-        if pf.ndim != 1 or any(a is not None and a.shape != (n,) for a in (pm, pd, pk, pw)):
-            raise ValueError("the pair arrays must be 1-d arrays of one length")
+        frames, (pf, pm, pd, pk), (pw,), n = _pairs.host_pairs(
+            frames, (pair_frame, pair_mixture, pair_density, pair_key), (pair_weight,))
         rc = self._lib.gmm_affine_accumulate_host(
             self._h, scorer.handle if scorer is not None else None, _ptr(frames), frames.shape[0], frames.shape[1],
             _ptr(pf), _ptr(pm), _ptr(pd), _ptr(pw), _ptr(pk), n)

@@ -7,13 +7,7 @@
 // 704-714): per pair D(D+1) + (D+1)^2 f64 multiply-multiply-adds for Z and G, and 2 D divisions for the shift kind.
 // As in gmm_kernels_adapt.hip nothing is scattered and no floating-point atomic is used: every cell of a set gathers
 // its own contributions in pair order, and the result is the header's numeric contract bit for bit.
-//   1. mllrResolve: a pair -> its set key * nLeaves + leafOfMixture[mixture], mean and covariance; a pair that is out
-//      of range in any way gets the sentinel set (the set count) and is counted with an integer atomic.  Its frame is
-//      never read.
-//   2. one stable radix sort of (set, pair index) by set (launchAccumSort of gmm_kernels_accum.hip).
-//   3. launchAffineIndexPieces of gmm_kernels_adapt.hip, the sets in the place of its keys: the sorted positions'
-//      frame, mean, covariance and weight gathered, and the first position of every piece of GMM_MLLR_CHUNK pairs of
-//      a set listed.
+//   passes 1-3 and 5: gmm_kernels_keyed.hip (the key of a pair is its set, key * nLeaves + the leaf of its mixture).
 //   4. mllrAccumulate: a workgroup per (piece, block of 256 cells of the set's one range, MllrLayout).  A lane owns one
 //      cell.  The piece's pairs are walked serially, a batch at a time: the workgroup stages per pair the row
 //      m | x | (f64)(x -f32 mu) | v (widened to f64) and the weight in LDS, then every lane runs its chain of dependent
@@ -22,7 +16,6 @@
 //      and v_d; shift: the difference and v_d), 1.0 for the full kind's count.  Piece 0 starts from the table's value
 //      and writes it back; a later piece starts from 0 and writes its row of the slab (the piece at sorted position i
 //      owns slot i / GMM_MLLR_CHUNK).
-//   5. mllrCombine: a set with more than one piece adds its slab rows to the table in piece order.
 // Every operation of the contract is an _rn intrinsic and the unit is built with -ffp-contract=off: the correctly
 // rounded f64 division expands into fused multiply-adds of its own, the contract's multiplies and adds never fuse.
 #include <hip/hip_runtime.h>
@@ -31,45 +24,6 @@
 
 namespace rasr_gmm {
 namespace dev {
-
-__global__ __launch_bounds__(256) void mllrResolve(MllrResolveArgs a) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-    if (p >= a.nPairs)
-        return;
-    const uint32_t f = a.pairFrame[p], m = a.pairMix[p];
-    const uint32_t key = a.pairKey ? a.pairKey[p] : 0u;
-    uint32_t       ks = a.nKeys * a.nLeaves, km = 0, kc = 0;  // skipped
-    bool           ok = f < a.nFrames && m < a.nMix && key < a.nKeys;
-    if (ok) {
-        const uint32_t e0 = a.mixOff[m], e1 = a.mixOff[m + 1];
-        const uint32_t d  = a.pairDensity ? a.pairDensity[p] : 0u;  // 0xffffffff (no best density) is out of range
-        ok                = d < e1 - e0;
-        if (ok) {
-            ks = key * a.nLeaves + a.leafOfMixture[m];
-            km = a.entryMean[e0 + d];
-            kc = a.entryCov[e0 + d];
-        }
-    }
-    a.set[p]       = ks;
-    a.mean[p]      = km;
-    a.cov[p]       = kc;
-    a.pairIndex[p] = p;
-    if (!ok)
-        atomicAdd(a.skipped, 1ull);
-}
-
-// pairs of the piece that starts at sorted position i with set k: the positions [i, i + n) hold k, n <= kMllrChunk
-__device__ __forceinline__ uint32_t pieceLength(const uint32_t* sets, uint32_t i, uint32_t k, uint32_t nPairs) {
-    uint32_t lo = i + 1, hi = min(i + kMllrChunk, nPairs);  // the first position past i whose set is not k
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (sets[mid] == k)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo - i;
-}
 
 enum : uint32_t { kCellMul = 0, kCellDiv = 1, kCellOne = 2 };
 
@@ -109,7 +63,7 @@ __global__ __launch_bounds__(256) void mllrAccumulate(MllrArgs a, uint32_t batch
             ib = vOff + (s - 1 - D);
         }
     }
-    double* dst = first ? a.tables + static_cast<size_t>(set) * C : a.slab + static_cast<size_t>(i / kMllrChunk) * C;
+    double* dst = first ? a.tables + static_cast<size_t>(set) * C : a.slab + static_cast<size_t>(i / kPieceChunk) * C;
     double  acc = first && act ? dst[c] : 0.0;
 
     for (uint32_t b0 = 0; b0 < n; b0 += batch) {
@@ -150,34 +104,7 @@ __global__ __launch_bounds__(256) void mllrAccumulate(MllrArgs a, uint32_t batch
         dst[c] = acc;
 }
 
-// grid: x the piece, y the block of cells; tables [nSets][cells], slab [slots][cells]
-__global__ __launch_bounds__(256) void mllrCombine(MllrArgs a) {
-    if (blockIdx.x >= min(*a.nPieces, a.maxPieces))
-        return;
-    const uint32_t i = a.pieces[blockIdx.x];
-    if (i + kMllrChunk >= a.nPairs)
-        return;
-    const uint32_t set = a.setsSorted[i];
-    if ((i > 0 && a.setsSorted[i - 1] == set) || a.setsSorted[i + kMllrChunk] != set)
-        return;  // not the first piece of a set with a second piece
-    const size_t cells = a.layout.cells();
-    const size_t c     = static_cast<size_t>(blockIdx.y) * kMllrBlock + threadIdx.x;
-    if (c >= cells)
-        return;
-    double acc = a.tables[static_cast<size_t>(set) * cells + c];
-    for (uint32_t pos = i + kMllrChunk; pos < a.nPairs && a.setsSorted[pos] == set; pos += kMllrChunk)
-        acc = __dadd_rn(acc, a.slab[static_cast<size_t>(pos / kMllrChunk) * cells + c]);
-    a.tables[static_cast<size_t>(set) * cells + c] = acc;
-}
-
 }  // namespace dev
-
-int launchMllrResolve(const MllrResolveArgs& a, ihipStream_t* stream) {
-    if (a.nPairs == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(dev::mllrResolve, dim3((a.nPairs + 255u) / 256u), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
 
 int launchMllrAccumulate(const MllrArgs& a, ihipStream_t* stream) {
     if (a.nPairs == 0 || a.maxPieces == 0)
@@ -187,15 +114,6 @@ int launchMllrAccumulate(const MllrArgs& a, ihipStream_t* stream) {
     const size_t   C     = a.layout.cells();
     hipLaunchKernelGGL(dev::mllrAccumulate, dim3(a.maxPieces, static_cast<uint32_t>((C + kMllrBlock - 1) / kMllrBlock)),
                        dim3(kMllrBlock), lds, stream, a, batch);
-    return hipGetLastError();
-}
-
-int launchMllrCombine(const MllrArgs& a, ihipStream_t* stream) {
-    if (a.nPairs <= kMllrChunk)  // no set has a second piece
-        return hipSuccess;
-    const size_t C = a.layout.cells();
-    hipLaunchKernelGGL(dev::mllrCombine, dim3(a.maxPieces, static_cast<uint32_t>((C + kMllrBlock - 1) / kMllrBlock)),
-                       dim3(kMllrBlock), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -16,12 +16,11 @@ import os
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _pairs
 from .mixture_set import MixtureSet, _from_desc, estimator_config
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+_ptr = _pairs.ptr
 
 
 class Estimator:
@@ -65,44 +64,20 @@ class Estimator:
         int32 or uint32 cuda tensors of n_pairs; pair_weight a float64 cuda tensor or None (weight 1).  Without
         pair_density the density is the scorer's best density of the pair (`scorer`: a Scorer), or, without a scorer,
         the only density of the mixture.  Asynchronous on `stream` (torch stream or raw handle)."""
-        import torch
         f = int(frames.shape[0] if n_frames is None else n_frames)
-        n = int(pair_frame.numel())
-        if frames.dtype != torch.float32 or frames.dim() != 2 or frames.stride(1) != 1:
-            raise ValueError("frames must be a float32 [F, >= D] tensor with unit column stride")
-        for name, t in (("pair_frame", pair_frame), ("pair_mixture", pair_mixture), ("pair_density", pair_density)):
-            if t is not None and (t.numel() != n or t.element_size() != 4 or t.dtype.is_floating_point
-                                  or not t.is_contiguous()):
-                raise ValueError(f"{name} must be a contiguous int32 / uint32 tensor of n_pairs entries")
-        if pair_weight is not None and (pair_weight.numel() != n or pair_weight.dtype != torch.float64
-                                        or not pair_weight.is_contiguous()):
-            raise ValueError("pair_weight must be a contiguous float64 tensor of n_pairs entries")
-        if stream is None:
-            stream = torch.cuda.current_stream(frames.device)
-        s = getattr(stream, "cuda_stream", stream)
-
-        def p(t):
-            return None if t is None else ctypes.c_void_p(t.data_ptr())
+        n, s, p = _pairs.device_pairs(
+            frames, (("pair_frame", pair_frame), ("pair_mixture", pair_mixture), ("pair_density", pair_density)),
+            (("pair_weight", pair_weight),), stream)
         rc = self._lib.gmm_estimator_accumulate_device(
-            self._h, scorer.handle if scorer is not None else None, p(frames), f, int(frames.stride(0)), p(pair_frame),
-            p(pair_mixture), p(pair_density), p(pair_weight), n, ctypes.c_void_p(s) if s else None)
+            self._h, scorer.handle if scorer is not None else None, p[0], f, int(frames.stride(0)), *p[1:], n, s)
         _capi.check(rc, "gmm_estimator_accumulate_device")
 
     def accumulate_host(self, frames, pair_frame, pair_mixture, pair_density=None, pair_weight=None, scorer=None) -> None:
         """gmm_estimator_accumulate_host: the same call on numpy arrays, synchronous."""
-        frames = np.ascontiguousarray(frames, dtype=np.float32)
-        if frames.ndim != 2:
-            raise ValueError("frames must be [F, >= D]")
-        pf = np.ascontiguousarray(pair_frame, dtype=np.uint32)
-        pm = np.ascontiguousarray(pair_mixture, dtype=np.uint32)
-        pd = None if pair_density is None else np.ascontiguousarray(pair_density, dtype=np.uint32)
-        pw = None if pair_weight is None else np.ascontiguousarray(pair_weight, dtype=np.float64)
-        n = pf.shape[0]
-        if pf.ndim != 1 or any(a is not None and a.shape != (n,) for a in (pm, pd, pw)):
-            raise ValueError("the pair arrays must be 1-d arrays of one length")
+        frames, lists, weights, n = _pairs.host_pairs(frames, (pair_frame, pair_mixture, pair_density), (pair_weight,))
         rc = self._lib.gmm_estimator_accumulate_host(
             self._h, scorer.handle if scorer is not None else None, _ptr(frames), frames.shape[0], frames.shape[1],
-            _ptr(pf), _ptr(pm), _ptr(pd), _ptr(pw), n)
+            *map(_ptr, lists + weights), n)
         _capi.check(rc, "gmm_estimator_accumulate_host")
 
     def accumulate_posteriors_device(self, frames, pair_frame, pair_mixture, pair_weight=None, scorer=None,
@@ -111,104 +86,47 @@ class Estimator:
         its mixture by the posteriors of `scorer` (a diagonal-sum Scorer; without one every mixture holds one density
         of posterior 1); a contribution counts iff pair_weight * posterior > weight_threshold (None: the default,
         DEFAULT_WEIGHT_THRESHOLD).  Tensors as accumulate_device; needs n_pairs * (largest mixture) <= max_pairs."""
-        import torch
         f = int(frames.shape[0] if n_frames is None else n_frames)
-        n = int(pair_frame.numel())
-        if frames.dtype != torch.float32 or frames.dim() != 2 or frames.stride(1) != 1:
-            raise ValueError("frames must be a float32 [F, >= D] tensor with unit column stride")
-        for name, t in (("pair_frame", pair_frame), ("pair_mixture", pair_mixture)):
-            if t.numel() != n or t.element_size() != 4 or t.dtype.is_floating_point or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous int32 / uint32 tensor of n_pairs entries")
-        if pair_weight is not None and (pair_weight.numel() != n or pair_weight.dtype != torch.float64
-                                        or not pair_weight.is_contiguous()):
-            raise ValueError("pair_weight must be a contiguous float64 tensor of n_pairs entries")
-        if stream is None:
-            stream = torch.cuda.current_stream(frames.device)
-        s = getattr(stream, "cuda_stream", stream)
+        n, s, p = _pairs.device_pairs(frames, (("pair_frame", pair_frame), ("pair_mixture", pair_mixture)),
+                                      (("pair_weight", pair_weight),), stream)
         thr = _capi.DEFAULT_WEIGHT_THRESHOLD if weight_threshold is None else float(weight_threshold)
-
-        def p(t):
-            return None if t is None else ctypes.c_void_p(t.data_ptr())
         rc = self._lib.gmm_estimator_accumulate_posteriors_device(
-            self._h, scorer.handle if scorer is not None else None, p(frames), f, int(frames.stride(0)), p(pair_frame),
-            p(pair_mixture), p(pair_weight), n, thr, ctypes.c_void_p(s) if s else None)
+            self._h, scorer.handle if scorer is not None else None, p[0], f, int(frames.stride(0)), *p[1:], n, thr, s)
         _capi.check(rc, "gmm_estimator_accumulate_posteriors_device")
 
     def accumulate_posteriors_host(self, frames, pair_frame, pair_mixture, pair_weight=None, scorer=None,
                                    weight_threshold=None) -> None:
         """gmm_estimator_accumulate_posteriors_host: the same call on numpy arrays, synchronous."""
-        frames = np.ascontiguousarray(frames, dtype=np.float32)
-        if frames.ndim != 2:
-            raise ValueError("frames must be [F, >= D]")
-        pf = np.ascontiguousarray(pair_frame, dtype=np.uint32)
-        pm = np.ascontiguousarray(pair_mixture, dtype=np.uint32)
-        pw = None if pair_weight is None else np.ascontiguousarray(pair_weight, dtype=np.float64)
-        n = pf.shape[0]
-        if pf.ndim != 1 or any(a is not None and a.shape != (n,) for a in (pm, pw)):
-            raise ValueError("the pair arrays must be 1-d arrays of one length")
+        frames, lists, weights, n = _pairs.host_pairs(frames, (pair_frame, pair_mixture), (pair_weight,))
         thr = _capi.DEFAULT_WEIGHT_THRESHOLD if weight_threshold is None else float(weight_threshold)
         rc = self._lib.gmm_estimator_accumulate_posteriors_host(
             self._h, scorer.handle if scorer is not None else None, _ptr(frames), frames.shape[0], frames.shape[1],
-            _ptr(pf), _ptr(pm), _ptr(pw), n, thr)
+            *map(_ptr, lists + weights), n, thr)
         _capi.check(rc, "gmm_estimator_accumulate_posteriors_host")
 
     # ---- discriminative training: numerator and denominator weights in one call ----
-
-    @staticmethod
-    def _check_device_pairs(frames, pair_frame, lists, weights):
-        import torch
-        n = int(pair_frame.numel())
-        if frames.dtype != torch.float32 or frames.dim() != 2 or frames.stride(1) != 1:
-            raise ValueError("frames must be a float32 [F, >= D] tensor with unit column stride")
-        for name, t in lists:
-            if t is not None and (t.numel() != n or t.element_size() != 4 or t.dtype.is_floating_point
-                                  or not t.is_contiguous()):
-                raise ValueError(f"{name} must be a contiguous int32 / uint32 tensor of n_pairs entries")
-        for name, t in weights:
-            if t is not None and (t.numel() != n or t.dtype != torch.float64 or not t.is_contiguous()):
-                raise ValueError(f"{name} must be a contiguous float64 tensor of n_pairs entries")
-        return n
 
     def accumulate_discriminative_device(self, frames, pair_frame, pair_mixture, pair_density=None, pair_weight_num=None,
                                          pair_weight_den=None, scorer=None, stream=None, n_frames=None) -> None:
         """gmm_estimator_accumulate_discriminative_device (Viterbi mode): accumulate_device with a numerator and a
         denominator weight per pair (float64 cuda tensors).  A side given as None receives nothing (both None is an
         error); a NaN weight marks the pair as absent on that side."""
-        import torch
         f = int(frames.shape[0] if n_frames is None else n_frames)
-        n = self._check_device_pairs(
-            frames, pair_frame,
-            (("pair_frame", pair_frame), ("pair_mixture", pair_mixture), ("pair_density", pair_density)),
-            (("pair_weight_num", pair_weight_num), ("pair_weight_den", pair_weight_den)))
-        if stream is None:
-            stream = torch.cuda.current_stream(frames.device)
-        s = getattr(stream, "cuda_stream", stream)
-
-        def p(t):
-            return None if t is None else ctypes.c_void_p(t.data_ptr())
+        n, s, p = _pairs.device_pairs(
+            frames, (("pair_frame", pair_frame), ("pair_mixture", pair_mixture), ("pair_density", pair_density)),
+            (("pair_weight_num", pair_weight_num), ("pair_weight_den", pair_weight_den)), stream)
         rc = self._lib.gmm_estimator_accumulate_discriminative_device(
-            self._h, scorer.handle if scorer is not None else None, p(frames), f, int(frames.stride(0)), p(pair_frame),
-            p(pair_mixture), p(pair_density), p(pair_weight_num), p(pair_weight_den), n,
-            ctypes.c_void_p(s) if s else None)
+            self._h, scorer.handle if scorer is not None else None, p[0], f, int(frames.stride(0)), *p[1:], n, s)
         _capi.check(rc, "gmm_estimator_accumulate_discriminative_device")
 
     def accumulate_discriminative_host(self, frames, pair_frame, pair_mixture, pair_density=None, pair_weight_num=None,
                                        pair_weight_den=None, scorer=None) -> None:
         """gmm_estimator_accumulate_discriminative_host: the same call on numpy arrays, synchronous."""
-        frames = np.ascontiguousarray(frames, dtype=np.float32)
-        if frames.ndim != 2:
-            raise ValueError("frames must be [F, >= D]")
-        pf = np.ascontiguousarray(pair_frame, dtype=np.uint32)
-        pm = np.ascontiguousarray(pair_mixture, dtype=np.uint32)
-        pd = None if pair_density is None else np.ascontiguousarray(pair_density, dtype=np.uint32)
-        wn = None if pair_weight_num is None else np.ascontiguousarray(pair_weight_num, dtype=np.float64)
-        wd = None if pair_weight_den is None else np.ascontiguousarray(pair_weight_den, dtype=np.float64)
-        n = pf.shape[0]
-        if pf.ndim != 1 or any(a is not None and a.shape != (n,) for a in (pm, pd, wn, wd)):
-            raise ValueError("the pair arrays must be 1-d arrays of one length")
+        frames, lists, weights, n = _pairs.host_pairs(frames, (pair_frame, pair_mixture, pair_density),
+                                                      (pair_weight_num, pair_weight_den))
         rc = self._lib.gmm_estimator_accumulate_discriminative_host(
             self._h, scorer.handle if scorer is not None else None, _ptr(frames), frames.shape[0], frames.shape[1],
-            _ptr(pf), _ptr(pm), _ptr(pd), _ptr(wn), _ptr(wd), n)
+            *map(_ptr, lists + weights), n)
         _capi.check(rc, "gmm_estimator_accumulate_discriminative_host")
 
     def accumulate_discriminative_posteriors_device(self, frames, pair_frame, pair_mixture, pair_weight_num=None,
@@ -217,40 +135,23 @@ class Estimator:
         """gmm_estimator_accumulate_discriminative_posteriors_device (Baum-Welch mode): the density posteriors of
         `scorer` are computed once per pair; a contribution is live on a side iff that side's pair weight * posterior
         > weight_threshold.  Tensors as accumulate_discriminative_device."""
-        import torch
         f = int(frames.shape[0] if n_frames is None else n_frames)
-        n = self._check_device_pairs(
-            frames, pair_frame, (("pair_frame", pair_frame), ("pair_mixture", pair_mixture)),
-            (("pair_weight_num", pair_weight_num), ("pair_weight_den", pair_weight_den)))
-        if stream is None:
-            stream = torch.cuda.current_stream(frames.device)
-        s = getattr(stream, "cuda_stream", stream)
+        n, s, p = _pairs.device_pairs(
+            frames, (("pair_frame", pair_frame), ("pair_mixture", pair_mixture)),
+            (("pair_weight_num", pair_weight_num), ("pair_weight_den", pair_weight_den)), stream)
         thr = _capi.DEFAULT_WEIGHT_THRESHOLD if weight_threshold is None else float(weight_threshold)
-
-        def p(t):
-            return None if t is None else ctypes.c_void_p(t.data_ptr())
         rc = self._lib.gmm_estimator_accumulate_discriminative_posteriors_device(
-            self._h, scorer.handle if scorer is not None else None, p(frames), f, int(frames.stride(0)), p(pair_frame),
-            p(pair_mixture), p(pair_weight_num), p(pair_weight_den), n, thr, ctypes.c_void_p(s) if s else None)
+            self._h, scorer.handle if scorer is not None else None, p[0], f, int(frames.stride(0)), *p[1:], n, thr, s)
         _capi.check(rc, "gmm_estimator_accumulate_discriminative_posteriors_device")
 
     def accumulate_discriminative_posteriors_host(self, frames, pair_frame, pair_mixture, pair_weight_num=None,
                                                   pair_weight_den=None, scorer=None, weight_threshold=None) -> None:
         """gmm_estimator_accumulate_discriminative_posteriors_host: the same call on numpy arrays, synchronous."""
-        frames = np.ascontiguousarray(frames, dtype=np.float32)
-        if frames.ndim != 2:
-            raise ValueError("frames must be [F, >= D]")
-        pf = np.ascontiguousarray(pair_frame, dtype=np.uint32)
-        pm = np.ascontiguousarray(pair_mixture, dtype=np.uint32)
-        wn = None if pair_weight_num is None else np.ascontiguousarray(pair_weight_num, dtype=np.float64)
-        wd = None if pair_weight_den is None else np.ascontiguousarray(pair_weight_den, dtype=np.float64)
-        n = pf.shape[0]
-        if pf.ndim != 1 or any(a is not None and a.shape != (n,) for a in (pm, wn, wd)):
-            raise ValueError("the pair arrays must be 1-d arrays of one length")
+        frames, lists, weights, n = _pairs.host_pairs(frames, (pair_frame, pair_mixture), (pair_weight_num, pair_weight_den))
         thr = _capi.DEFAULT_WEIGHT_THRESHOLD if weight_threshold is None else float(weight_threshold)
         rc = self._lib.gmm_estimator_accumulate_discriminative_posteriors_host(
             self._h, scorer.handle if scorer is not None else None, _ptr(frames), frames.shape[0], frames.shape[1],
-            _ptr(pf), _ptr(pm), _ptr(wn), _ptr(wd), n, thr)
+            *map(_ptr, lists + weights), n, thr)
         _capi.check(rc, "gmm_estimator_accumulate_discriminative_posteriors_host")
 
     def accumulate_objective(self, f: float) -> None:
