@@ -50,7 +50,7 @@ EBWEST   = $(BUILD)/tests/ebw_estimate_test
 MLLREST  = $(BUILD)/tests/mllr_estimate_test
 PAIRTOPO = $(BUILD)/tests/pair_topology_test
 
-all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) $(EBWEST) $(MLLREST) $(PAIRTOPO) oracle check-integration
+all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) $(EBWEST) $(MLLREST) $(PAIRTOPO) oracle reference-scorers check-integration
 
 $(BUILD)/gmm_kernels_i8.o: $(SRC)/gmm_kernels_i8.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -269,6 +269,15 @@ $(DRIVER): tests/cpp/feature_scorer_driver.cc $(LIB) $(HDRS)
 oracle:
 	$(MAKE) -C oracle
 
+# The reference's OWN scorers as a stand-alone executable, oracle/_ref/ref_scorers (test infrastructure: what the
+# oracle is pinned to, tests/test_reference_pin.py; recipe and flags in oracle/ref/Makefile).  Built where
+# $(RASR_REF)/src exists; elsewhere (the GPU box) nothing happens and an executable already there stays.  A
+# failure here never fails the build: the tests that need the executable then say why they skip.
+RASR_REF ?= /root/reference
+reference-scorers:
+	@$(MAKE) -s -C oracle/ref RASR_REF=$(RASR_REF) all || \
+	    echo "reference-scorers: build failed; the live reference pin will skip (fixtures under tests/golden/ref still run)"
+
 # The RASR-side adapter (integration/rasr/Mm/GpuFeatureScorer.{hh,cc}) compiled -fsyntax-only against the
 # reference's own headers with the reference's flags (config/cc-gcc.make:26-29).  Core/Utility.hh includes the
 # make-generated Modules.hh, so a one-line stand-in (MODULE_MM_BATCH, as src/Mm/Makefile:70-75 builds it) is
@@ -345,4 +354,4 @@ clean:
 print-%:
 	@echo '$($*)'
 
-.PHONY: all oracle clean check-integration check-integration-link
+.PHONY: all oracle reference-scorers clean check-integration check-integration-link

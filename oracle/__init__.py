@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE ONLY -- ctypes binding of the CPU restatement (oracle/gmm_oracle.c).
 
-Parity status: UNPINNED (see gmm_oracle.h).  Only tests/, __graft_entry__.smoke()
+Parity status: pinned to the reference's compiled scorers (see gmm_oracle.h, oracle/reference.py).  Only tests/, __graft_entry__.smoke()
 and bench.py's cpu_baseline leg may import this package.
 """
 from .oracle import (OracleFloat, OracleFloatSum, OraclePresel, OracleSimd, libc_rand_sequence, batch_fast_score, batch_float_score, batch_int_prepare, batch_int_score, build,

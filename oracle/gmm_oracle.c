@@ -1,6 +1,6 @@
 /*
  * gmm_oracle.c -- TEST INFRASTRUCTURE ONLY (parity checker + CPU baseline "port").
- * See gmm_oracle.h for scope and the PARITY UNPINNED status.
+ * See gmm_oracle.h for scope and the parity status.
  *
  * Build (oracle/Makefile): gcc -std=gnu99 -O2 -ffast-math -msse3 -funsigned-char
  * i.e. the reference's own flags (config/cc-gcc.make:26-29, config/proc-x86_64.make:13-20,31),
@@ -669,6 +669,20 @@ typedef struct {
     float    backoff;
 } orc_bflt_ctx;
 
+/* cc:226 `_mm_min_ps(_mm_load_ss(score), s1)` as the reference's build computes it.  Under -ffast-math GCC takes
+ * the minps builtin for commutative and emits `minps score, sum` with the SUM as the destination operand
+ * (oracle/ref: the compiled fillScoreCacheTpl has `minps %xmm1,%xmm0`, xmm0 the sum), i.e. sum < score ? sum :
+ * score -- so a nan sum (nan frame) keeps the stored score, where the intrinsic as written would store the nan.
+ * Found by the reference pin (tests/test_reference_pin.py).  The nan is recognised by its bits: this file
+ * is compiled with -ffast-math, under which a floating-point comparison may be taken for nan-free by any compiler. */
+static float orc_min_sum_first(float sum, float score) {
+    uint32_t bits;
+    memcpy(&bits, &sum, sizeof(bits));
+    if ((bits & 0x7fffffffu) > 0x7f800000u)
+        return score; /* nan < score is false */
+    return sum < score ? sum : score;
+}
+
 static void orc_bflt_frames(void* p, uint32_t t0, uint32_t t1) {
     const orc_bflt_ctx* x = (const orc_bflt_ctx*)p;
     float*   feature = (float*)malloc(sizeof(float) * x->Dp);
@@ -704,7 +718,7 @@ static void orc_bflt_frames(void* p, uint32_t t0, uint32_t t1) {
                 s1 = r + s1;
                 r = (v4sf){s1[1], s1[0], s1[3], s1[2]};
                 s1 = r + s1;
-                score = score < s1[0] ? score : s1[0]; /* _mm_min_ps(load_ss(score), s1) lane 0 */
+                score = orc_min_sum_first(s1[0], score); /* _mm_min_ps(load_ss(score), s1) lane 0 */
             }
             if (score < FLT_MAX)
                 score *= 0.5;

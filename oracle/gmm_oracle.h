@@ -6,11 +6,15 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it.
  * Nothing in rasr_amd/ links or calls it.
  *
- * PARITY STATUS: UNPINNED.  The reference hot path cannot be built in this
- * image without stand-ins for generated code (src/Core/Utility.hh:18 needs the
- * make-generated Modules.hh, src/Core/Configuration.cc:26 the bison-generated
- * ArithmeticExpressionParser.hh; bison is absent), and the reference holds no
- * tests, golden vectors or fixtures for src/Mm scorers.
+ * PARITY STATUS: PINNED to the reference's own compiled scorers.  The recipe
+ * oracle/ref/ builds the reference's sources (with stand-ins for its three
+ * generated files) into the stand-alone oracle/_ref/ref_scorers;
+ * tests/test_reference_pin.py compares every scorer restated here with it on
+ * its sweep -- bit-equal for all eight types, float types included, on
+ * GenuineIntel and AuthenticAMD hosts -- and tests/golden/ref/ freezes replies
+ * of that executable.  One mismatch was found and fixed
+ * (orc_min_sum_first in gmm_oracle.c).  Not pinned: the estimator, EBW, CMLLR,
+ * MLLR and state-posterior restatements elsewhere in the tests.
  * The restatement follows the reference source line by line (citations below)
  * and is compiled with the reference's own flags (config/cc-gcc.make,
  * config/proc-x86_64.make: -O2 -ffast-math -msse3 -funsigned-char) so that

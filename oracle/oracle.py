@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY -- ctypes binding of oracle/_build/libgmm_oracle.so.
 
 CPU restatement of RASR's feature scorers (parity checker + CPU baseline).
-Parity status: UNPINNED (gmm_oracle.h explains why).  Works on any object with
+Parity status: pinned by tests/test_reference_pin.py (gmm_oracle.h).  Works on any object with
 the MixtureSet attributes (means, variances, density_mean, density_covariance,
 mixture_offsets, mixture_densities, mixture_log_weights).
 """
@@ -381,7 +381,7 @@ class OraclePresel:
             self.dp = (D + 7) // 8 * 8
             self.variance = np.zeros(self.dp, np.float32)
             self.means = np.zeros((E, self.dp), np.float32)
-            consts = np.zeros(E, np.float32)
+            consts = self.constants = np.zeros(E, np.float32)  # logNormFactor - 2 logWeight (cc:174)
             rc = lib.orc_batch_float_tables(ctypes.byref(self._d.c), self.variance.ctypes.data_as(_vp),
                                             self.means.ctypes.data_as(_vp), consts.ctypes.data_as(_vp))
         else:

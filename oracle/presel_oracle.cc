@@ -9,7 +9,7 @@
 // the same comparator; the clustering calls the same srand/rand.  Built with the reference's flags
 // (oracle/Makefile: -O2 -ffast-math -msse3 -funsigned-char).
 //
-// Parity status: UNPINNED (gmm_oracle.h); the tie order is pinned to this image's libstdc++ (GCC 11)
+// Parity status: pinned to the reference's compiled clustering and selection (gmm_oracle.h); the tie order is pinned to this image's libstdc++ (GCC 11)
 // and glibc, the reference build's own runtime on Linux.
 #include <stdint.h>
 #include <stdlib.h>

@@ -91,6 +91,12 @@ __device__ __forceinline__ uint16_t h16bits(float v) {
 // builds its 8-value groups of K.  (One thread per frame walking K serially took 22 us for a 1-frame call,
 // most of a small host call's device time: profiles/r04/s14.)
 // ---------------------------------------------------------------------------
+// frameExp of a frame that holds an infinity (or overflows one) and no nan.  Its fragments are built with e = 0 and
+// carry nans (hi = inf, lo = inf - inf), so the diagonal-maximum kernels find no finite candidate whatever the
+// exponent; the diagonal-sum kernels read the mark and return the reference's +inf (every density score is +inf:
+// FLT_MAX - log(0), GaussDiagonalMaximumFeatureScorer.cc:263-289) where the log-sum alone would give nan.
+constexpr int32_t kSplitInfFrame = 0x40000000;
+
 template <int ROWS>
 __global__ __launch_bounds__(256) void prepareFramesSplit(const float* __restrict__ frames, uint32_t nFrames,
                                                            uint32_t frameStride, uint32_t nFramesRead, uint32_t D,
@@ -108,19 +114,21 @@ __global__ __launch_bounds__(256) void prepareFramesSplit(const float* __restric
     const bool       inRange = f < nFramesRead, valid = f < nFrames;
     const float*     x       = frames + static_cast<size_t>(f) * frameStride;
     float            ymax    = 0.0f;
-    int              finite  = 1;
+    int              finite  = 1, nanFree = 1;
     if (valid)
         for (uint32_t k = t; k < D; k += 32u) {
             const float v = __fmul_rn(__fsub_rn(x[k], centre[k]), isv[k]);  // x' as the f32 kernel forms it
             xs[fl][k]     = v;
             const float y = fabsf(v * dimScale[k]);
             finite        = finite && y <= 3.40282347e+38f;
+            nanFree       = nanFree && y == y;
             ymax          = fmaxf(ymax, y);
         }
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) {
-        ymax   = fmaxf(ymax, __shfl_xor(ymax, o, 32));
-        finite = finite & __shfl_xor(finite, o, 32);
+        ymax    = fmaxf(ymax, __shfl_xor(ymax, o, 32));
+        finite  = finite & __shfl_xor(finite, o, 32);
+        nanFree = nanFree & __shfl_xor(nanFree, o, 32);
     }
     __syncthreads();
     if (t == 0 && inRange) {
@@ -141,7 +149,7 @@ __global__ __launch_bounds__(256) void prepareFramesSplit(const float* __restric
         }
         const float xxs = ldexpf(xx, -e);
         frameXX[f]      = xxs;
-        frameExp[f]     = e;
+        frameExp[f]     = (valid && !finite && nanFree) ? kSplitInfFrame : e;  // the fragments keep e = 0
         shXX[fl]        = xxs;
         shE[fl]         = e;
     }
@@ -210,7 +218,7 @@ __global__ __launch_bounds__(256) void prepareFramesSplitCov(const float* __rest
     const bool       inRange = f < nFramesRead, valid = f < nFrames;
     const float*     x       = frames + static_cast<size_t>(f) * frameStride;
     float            ymax    = 0.0f;
-    int              finite  = 1;
+    int              finite  = 1, nanFree = 1;
     if (valid)
         for (uint32_t k = t; k < D; k += 32u) {
             const float y = __fsub_rn(x[k], centre[k]);
@@ -218,12 +226,14 @@ __global__ __launch_bounds__(256) void prepareFramesSplitCov(const float* __rest
             const float a = fabsf(__fmul_rn(__fmul_rn(y, y), dimScale[k]));
             const float b = fabsf(__fmul_rn(y, dimScale[D + k]));
             finite        = finite && a <= 3.40282347e+38f && b <= 3.40282347e+38f;
+            nanFree       = nanFree && a == a && b == b;
             ymax          = fmaxf(ymax, fmaxf(a, b));
         }
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) {
-        ymax   = fmaxf(ymax, __shfl_xor(ymax, o, 32));
-        finite = finite & __shfl_xor(finite, o, 32);
+        ymax    = fmaxf(ymax, __shfl_xor(ymax, o, 32));
+        finite  = finite & __shfl_xor(finite, o, 32);
+        nanFree = nanFree & __shfl_xor(nanFree, o, 32);
     }
     if (t == 0 && inRange) {
         int e = 0;
@@ -232,7 +242,7 @@ __global__ __launch_bounds__(256) void prepareFramesSplitCov(const float* __rest
             frexpf(ymax, &ex);  // ymax in [2^(ex-1), 2^ex)
             e = ex - 15;
         }
-        frameExp[f] = e;
+        frameExp[f] = (valid && !finite && nanFree) ? kSplitInfFrame : e;  // the fragments keep e = 0
         shE[fl]     = e;
     }
     __syncthreads();
@@ -1226,7 +1236,8 @@ __global__ __launch_bounds__(64 * (kSplitFramesPerBlock / (32 * GMM_SPLIT32_NB))
 template <bool BEST>
 __device__ __forceinline__ void emitMixtureSplitSum(const SplitArgs& a, const uint32_t (&best)[4][2],
                                                     const float (&S)[4][2], const float (&R)[4], uint32_t m,
-                                                    uint32_t frame0, int lane, uint32_t g, uint32_t kmask) {
+                                                    uint32_t frame0, int lane, uint32_t g, uint32_t kmask,
+                                                    bool infFrame) {
     uint32_t k[4];
     float    sum[4];
 #pragma unroll
@@ -1266,7 +1277,8 @@ __device__ __forceinline__ void emitMixtureSplitSum(const SplitArgs& a, const ui
     const float kv   = __uint_as_float((key & ~kmask) | ((kmask + 1u) >> 1));
     const bool  none = !(kv < 1e37f);  // empty mixture: R stays 1e30, S = 0 -> +inf, as the reference
     // -log sum exp(-s_d) = R ln2 - K0/2 - ln S  (ln S = log2 S * ln2)
-    const float score = __fmul_rn(a.outScale, (rf - __builtin_amdgcn_logf(sf)) * 0.693147181f - 0.5f * a.offsetK0);
+    const float score = __fmul_rn(a.outScale, infFrame ? __builtin_inff()
+                                                       : (rf - __builtin_amdgcn_logf(sf)) * 0.693147181f - 0.5f * a.offsetK0);
     const uint32_t idx = none ? 0xffffffffu : ((((key & kmask) >> 2) << 4) | (grp << 2) | (key & 3u));
     const uint32_t mo  = m - a.mixBase;
     const uint32_t off = static_cast<uint32_t>(frame0 + lane) * 4u;
@@ -1314,8 +1326,13 @@ __global__ __launch_bounds__(kSplitFramesPerBlock / GMM_SPLIT_SUM_NF * 4, GMM_SP
 #pragma unroll
         for (int s = 0; s < KS; ++s)
             B[cb][s] = fh[(static_cast<size_t>(fb0 + cb) * KS + s) * 64 + lane];
-        kap[cb] = ldexpf(0.721347520f, a.frameExp[frame0 + 16 * cb + (lane & 15)]);
+        const int32_t ef = a.frameExp[frame0 + 16 * cb + (lane & 15)];
+        kap[cb]          = ldexpf(0.721347520f, ef == kSplitInfFrame ? 0 : ef);
     }
+    bool infFrame[NH];  // the frame this lane emits in half h holds an infinity and no nan
+#pragma unroll
+    for (int h = 0; h < NH; ++h)
+        infFrame[h] = a.frameExp[frame0 + 64u * h + lane] == kSplitInfFrame;
 #pragma unroll
     for (int cb = 0; cb < NF; ++cb) {
 #pragma unroll
@@ -1359,7 +1376,7 @@ __global__ __launch_bounds__(kSplitFramesPerBlock / GMM_SPLIT_SUM_NF * 4, GMM_SP
             emitMixtureSplitSum<BEST>(a, *reinterpret_cast<const uint32_t(*)[4][2]>(&best[4 * h]),
                                       *reinterpret_cast<const float(*)[4][2]>(&S[4 * h]),
                                       *reinterpret_cast<const float(*)[4]>(&Rf[4 * h]), m, frame0 + 64u * h, lane, g,
-                                      kmask);
+                                      kmask, infFrame[h]);
     };
     const auto advance = [&](uint32_t tNext) {
         ++m;
@@ -1545,7 +1562,7 @@ __global__ __launch_bounds__(kSplitFramesPerBlock / GMM_SPLIT_SUM_NF * 4, GMM_SP
 template <bool BEST>
 __device__ __forceinline__ void emitMixtureSplit32Sum(const SplitArgs& a, const uint32_t (&best)[2][2],
                                                       const float (&S)[2][2], const float (&R)[2], uint32_t m,
-                                                      uint32_t frame0, int lane, uint32_t kmask) {
+                                                      uint32_t frame0, int lane, uint32_t kmask, bool infFrame) {
     uint32_t k[2];
     float    sum[2];
 #pragma unroll
@@ -1573,7 +1590,8 @@ __device__ __forceinline__ void emitMixtureSplit32Sum(const SplitArgs& a, const 
     const float kv   = __uint_as_float((key & ~kmask) | ((kmask + 1u) >> 1));
     const bool  none = !(kv < 1e37f);  // empty mixture: R stays 1e30, S = 0 -> +inf, as the reference
     // -log sum exp(-s_d) = R ln2 - K0/2 - ln S
-    const float score = __fmul_rn(a.outScale, (rf - __builtin_amdgcn_logf(sf)) * 0.693147181f - 0.5f * a.offsetK0);
+    const float score = __fmul_rn(a.outScale, infFrame ? __builtin_inff()
+                                                       : (rf - __builtin_amdgcn_logf(sf)) * 0.693147181f - 0.5f * a.offsetK0);
     const uint32_t idx = none ? 0xffffffffu : ((((key & kmask) >> 4) << 5) | row);
     const uint32_t mo  = m - a.mixBase;
     const uint32_t off = static_cast<uint32_t>(frame0 + lane) * 4u;
@@ -1621,8 +1639,13 @@ __global__ __launch_bounds__(64 * (kSplitFramesPerBlock / 128), 1) void scoreSpl
 #pragma unroll
         for (int s = 0; s < KS; ++s)
             B[b][s] = fh[(static_cast<size_t>(fb0 + b) * KS + s) * 64 + lane];
-        kap[b] = ldexpf(0.721347520f, a.frameExp[frame0 + 32u * b + (static_cast<uint32_t>(lane) & 31u)]);
+        const int32_t ef = a.frameExp[frame0 + 32u * b + (static_cast<uint32_t>(lane) & 31u)];
+        kap[b]           = ldexpf(0.721347520f, ef == kSplitInfFrame ? 0 : ef);
     }
+    bool infFrame[NH];  // the frame this lane emits in half h holds an infinity and no nan
+#pragma unroll
+    for (int h = 0; h < NH; ++h)
+        infFrame[h] = a.frameExp[frame0 + 64u * h + lane] == kSplitInfFrame;
     // frame operands complete before the tile prefetch, then pinned to the accumulator file
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
@@ -1698,7 +1721,7 @@ __global__ __launch_bounds__(64 * (kSplitFramesPerBlock / 128), 1) void scoreSpl
             emitMixtureSplit32Sum<BEST>(a, *reinterpret_cast<const uint32_t(*)[2][2]>(&best[2 * h]),
                                         *reinterpret_cast<const float(*)[2][2]>(&S[2 * h]),
                                         *reinterpret_cast<const float(*)[2]>(&Rf[2 * h]), m, frame0 + 64u * h, lane,
-                                        kmask);
+                                        kmask, infFrame[h]);
     };
     const auto advance = [&](uint32_t tNext) __attribute__((always_inline)) {
         ++m;

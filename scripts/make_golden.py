@@ -3,8 +3,8 @@
 
 These fixtures freeze the CPU restatement (oracle/gmm_oracle.c) as computed on the
 machine that generated them; they are regression vectors for the oracle and the
-product, NOT reference outputs (the reference cannot be built here; see
-oracle/gmm_oracle.h: parity unpinned).  The 1/sqrt(var) table depends on the CPU's
+product, NOT reference outputs (those are tests/golden/ref, written by
+scripts/make_ref_golden.py from the reference's compiled scorers).  The 1/sqrt(var) table depends on the CPU's
 rsqrtss (the reference's -ffast-math build uses it), so the table and the CPU
 vendor are stored and tests skip when a different rsqrtss is detected.
 """

@@ -7,7 +7,7 @@ Tolerances (written here):
     srand/rand and libstdc++'s std::sort (the tie order of equal distances is std::sort's);
   * preselection-batch-int scores: BIT-EXACT; preselection-batch-float scores: |gpu - ref| <=
     1e-4 * max(1, |ref|) like batch-float (split-f16 kernel), the backoff score exactly.
-Parity status: unpinned (gmm_oracle.h); the reference holds no fixtures for these scorers.
+Parity status: the oracle is pinned to the reference's compiled scorers (tests/test_reference_pin.py).
 """
 import ctypes
 import os
