@@ -30,7 +30,8 @@ OBJS      = $(BUILD)/gmm_kernels_i8.o $(BUILD)/gmm_kernels_f32.o $(BUILD)/gmm_ke
             $(BUILD)/gmm_kernels_state.o $(BUILD)/gmm_state.o \
             $(BUILD)/gmm_kernels_keyed.o $(BUILD)/gmm_pairaccum.o $(BUILD)/PairTopology.o \
             $(BUILD)/gmm_kernels_adapt.o $(BUILD)/gmm_adapt.o $(BUILD)/AffineTransformEstimate.o \
-            $(BUILD)/gmm_kernels_mllr.o $(BUILD)/gmm_mllr.o $(BUILD)/MllrEstimate.o
+            $(BUILD)/gmm_kernels_mllr.o $(BUILD)/gmm_mllr.o $(BUILD)/MllrEstimate.o \
+            $(BUILD)/gmm_kernels_align.o $(BUILD)/gmm_align.o $(BUILD)/AlignGraph.o
 # the core of the handles that accumulate pairs (gmm_pairaccum.hh names the chunk constants of both adaptation headers)
 PAIR_HDRS = $(SRC)/gmm_pairaccum.hh $(SRC)/host/PairTopology.hh $(SRC)/gmm_estimator.hh include/rasr_gmm_estimator.h \
             include/rasr_gmm_adaptation.h include/rasr_gmm_mllr.h
@@ -40,6 +41,8 @@ EST_HDRS  = $(PAIR_HDRS)
 ADAPT_HDRS = $(PAIR_HDRS) $(SRC)/gmm_adapt.hh
 # include/rasr_gmm_mllr.h: the units behind it depend on these besides HDRS
 MLLR_HDRS = $(PAIR_HDRS) $(SRC)/gmm_mllr.hh
+# include/rasr_gmm_align.h: the units behind it depend on these (the kernel unit on nothing else)
+ALIGN_HDRS = include/rasr_gmm_align.h include/rasr_gmm.h $(SRC)/gmm_align.hh $(SRC)/host/AlignGraph.hh
 DRIVER    = $(BUILD)/tests/feature_scorer_driver
 
 REFSORT   = $(BUILD)/tests/refsort_test
@@ -49,8 +52,9 @@ AFFINEEST = $(BUILD)/tests/affine_estimate_test
 EBWEST   = $(BUILD)/tests/ebw_estimate_test
 MLLREST  = $(BUILD)/tests/mllr_estimate_test
 PAIRTOPO = $(BUILD)/tests/pair_topology_test
+ALIGNGRAPH = $(BUILD)/tests/align_graph_test
 
-all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) $(EBWEST) $(MLLREST) $(PAIRTOPO) oracle reference-scorers check-integration
+all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) $(EBWEST) $(MLLREST) $(PAIRTOPO) $(ALIGNGRAPH) oracle reference-scorers check-integration
 
 $(BUILD)/gmm_kernels_i8.o: $(SRC)/gmm_kernels_i8.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -147,6 +151,20 @@ $(BUILD)/gmm_mllr.o: $(SRC)/gmm_mllr.cc $(HDRS) $(MLLR_HDRS)
 	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
 
 $(BUILD)/MllrEstimate.o: $(SRC)/host/MllrEstimate.cc include/rasr_gmm.h include/rasr_gmm_mllr.h
+	@mkdir -p $(BUILD)
+	g++ $(HOSTFLAGS) -c $< -o $@
+
+# Viterbi alignment over a score table (gmm_aligner_*): one workgroup per segment, f32 additions and comparisons only,
+# every one an _rn intrinsic.  Not one of KERNEL_OBJS
+$(BUILD)/gmm_kernels_align.o: $(SRC)/gmm_kernels_align.hip $(ALIGN_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/gmm_align.o: $(SRC)/gmm_align.cc $(HDRS) $(ALIGN_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
+
+$(BUILD)/AlignGraph.o: $(SRC)/host/AlignGraph.cc $(SRC)/host/AlignGraph.hh include/rasr_gmm.h include/rasr_gmm_align.h
 	@mkdir -p $(BUILD)
 	g++ $(HOSTFLAGS) -c $< -o $@
 
@@ -262,6 +280,20 @@ $(PAIRTOPO): tests/cpp/pair_topology_test.cc $(SRC)/host/PairTopology.cc $(SRC)/
 	@mkdir -p $(BUILD)/tests
 	g++ $(HOSTFLAGS) $(PAIRTOPO_FLAGS) -o $@ $< $(SRC)/host/PairTopology.cc
 
+# host check of the alignment graphs' validation and incoming-arc lists (no GPU, no HIP): the graph unit alone
+ALIGNGRAPH_SRCS = tests/cpp/align_graph_test.cc $(SRC)/host/AlignGraph.cc
+ALIGNGRAPH_DEPS = $(ALIGNGRAPH_SRCS) $(SRC)/host/AlignGraph.hh include/rasr_gmm.h include/rasr_gmm_align.h
+$(ALIGNGRAPH): $(ALIGNGRAPH_DEPS)
+	@mkdir -p $(BUILD)/tests
+	g++ $(HOSTFLAGS) -o $@ $(ALIGNGRAPH_SRCS)
+
+# the same program under the address and undefined-behaviour sanitizers, built and run on the CPU
+$(ALIGNGRAPH)_san: $(ALIGNGRAPH_DEPS)
+	@mkdir -p $(BUILD)/tests
+	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(ALIGNGRAPH_SRCS)
+check-align-graph: $(ALIGNGRAPH)_san
+	$(ALIGNGRAPH)_san
+
 $(DRIVER): tests/cpp/feature_scorer_driver.cc $(LIB) $(HDRS)
 	@mkdir -p $(BUILD)/tests
 	g++ $(HOSTFLAGS) -o $@ $< -L$(LIBDIR) -lrasr_gmm -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
@@ -354,4 +386,4 @@ clean:
 print-%:
 	@echo '$($*)'
 
-.PHONY: all oracle reference-scorers clean check-integration check-integration-link
+.PHONY: all oracle reference-scorers clean check-integration check-integration-link check-align-graph

@@ -25,6 +25,9 @@ GMM_MLLR_CHUNK = 512  # include/rasr_gmm_mllr.h: part of the MLLR accumulation's
 GMM_MLLR_FULL = 1  # the kinds of MLLR statistics (a mask for gmm_mllr_create)
 GMM_MLLR_SHIFT = 2
 GMM_MLLR_NO_ID = 0xFFFFFFFF  # "none" in the tree arrays of gmm_mllr_estimate
+GMM_ALIGN_MAX_STATES = 6144  # include/rasr_gmm_align.h: the most states of one segment
+GMM_ALIGN_MAX_IN_ARCS = 65535  # the most arcs entering one state
+GMM_ALIGN_NONE = 0xFFFFFFFF  # the per-frame outputs of a segment without an alignment
 STATE_POSTERIOR_CHUNK = 256  # include/rasr_gmm.h GMM_STATE_POSTERIOR_CHUNK: part of the state posteriors' contract
 # GMM_ESTIMATOR_DEFAULT_WEIGHT_THRESHOLD: Core::Type<f32>::epsilon, the Baum-Welch weightThreshold_
 DEFAULT_WEIGHT_THRESHOLD = 2.0 ** -23
@@ -126,6 +129,21 @@ class EbwConfig(ctypes.Structure):  # gmm_ebw_config
     ]
 
 
+class AlignGraphs(ctypes.Structure):  # gmm_align_graphs
+    _fields_ = [
+        ("n_segments", ctypes.c_uint32),
+        ("state_offset", ctypes.c_void_p),
+        ("arc_offset", ctypes.c_void_p),
+        ("arc_target", ctypes.c_void_p),
+        ("arc_mixture", ctypes.c_void_p),
+        ("arc_weight", ctypes.c_void_p),
+        ("initial_state", ctypes.c_void_p),
+        ("final_weight", ctypes.c_void_p),
+        ("frame_begin", ctypes.c_void_p),
+        ("n_frames", ctypes.c_void_p),
+    ]
+
+
 EBW_TYPES = {"global-rwth": 0, "local-rwth": 1, "cambridge": 2}
 
 GMM_HOST_KEEP_BEST = 1
@@ -136,7 +154,7 @@ GMM_HOST_ASYNC = 8
 GMM_EXCHANGE = {"auto": 0, "rccl": 1, "copy": 2}
 
 # (name, restype, argtypes) for every function declared in include/rasr_gmm.h, rasr_gmm_io.h, rasr_gmm_estimator.h,
-# rasr_gmm_adaptation.h and rasr_gmm_mllr.h
+# rasr_gmm_adaptation.h, rasr_gmm_mllr.h and rasr_gmm_align.h
 PROTOTYPES = [
     ("gmm_default_config", None, [ctypes.POINTER(ScorerConfig)]),
     ("gmm_scorer_create", ctypes.c_int,
@@ -339,6 +357,18 @@ PROTOTYPES = [
     ("gmm_mllr_adapt_means", ctypes.c_int,
      [ctypes.POINTER(MixtureSetDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int,
       ctypes.c_void_p]),
+    # include/rasr_gmm_align.h
+    ("gmm_aligner_create", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int,
+      ctypes.POINTER(ctypes.c_void_p)]),
+    ("gmm_aligner_destroy", ctypes.c_int, [ctypes.c_void_p]),
+    ("gmm_aligner_set_segments", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(AlignGraphs)]),
+    ("gmm_aligner_align_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("gmm_aligner_align_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("gmm_version", ctypes.c_char_p, []),
     ("gmm_kernel_id", ctypes.c_char_p, []),
 ]
