@@ -26,7 +26,7 @@ OBJS      = $(BUILD)/gmm_kernels_i8.o $(BUILD)/gmm_kernels_f32.o $(BUILD)/gmm_ke
             $(BUILD)/gmm_kernels_presel.o $(BUILD)/gmm_presel.o $(BUILD)/gmm_kernels_shard.o $(BUILD)/gmm_hostio.o \
             $(BUILD)/gmm_kernels_direct.o $(BUILD)/gmm_kernels_layout.o $(BUILD)/gmm_shard.o $(BUILD)/gmm_kernels_pairs.o \
             $(BUILD)/gmm_create.o $(BUILD)/gmm_score.o $(BUILD)/gmm_hostcall.o $(BUILD)/gmm_group.o \
-            $(BUILD)/gmm_kernels_accum.o $(BUILD)/gmm_kernels_accum_dual.o $(BUILD)/gmm_estimator.o $(BUILD)/gmm_kernels_posterior.o \
+            $(BUILD)/gmm_kernels_accum.o $(BUILD)/gmm_estimator.o $(BUILD)/gmm_kernels_posterior.o \
             $(BUILD)/gmm_kernels_state.o $(BUILD)/gmm_state.o \
             $(BUILD)/gmm_kernels_keyed.o $(BUILD)/gmm_pairaccum.o $(BUILD)/PairTopology.o \
             $(BUILD)/gmm_kernels_adapt.o $(BUILD)/gmm_adapt.o $(BUILD)/AffineTransformEstimate.o \
@@ -96,15 +96,10 @@ $(BUILD)/gmm_kernels_state.o: $(SRC)/gmm_kernels_state.hip $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# maximum-likelihood accumulation (gmm_estimator_accumulate_*): resolve, inverted indexes (rocPRIM radix sort),
-# ordered f64 sums.  Not one of KERNEL_OBJS: gmm_kernel_id names the scoring kernels the PMC summaries measure
+# maximum-likelihood and joint numerator / denominator accumulation (gmm_estimator_accumulate_*,
+# gmm_estimator_accumulate_discriminative_*): resolve, inverted indexes (rocPRIM radix sort), ordered f64 sums with one
+# or two chains per lane.  Not one of KERNEL_OBJS: gmm_kernel_id names the scoring kernels the PMC summaries measure
 $(BUILD)/gmm_kernels_accum.o: $(SRC)/gmm_kernels_accum.hip $(EST_HDRS)
-	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# joint numerator / denominator accumulation for discriminative training (gmm_estimator_accumulate_discriminative_*):
-# gmm_kernels_accum's passes with two f64 chains per lane.  Not one of KERNEL_OBJS
-$(BUILD)/gmm_kernels_accum_dual.o: $(SRC)/gmm_kernels_accum_dual.hip $(EST_HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -10,6 +10,68 @@
 
 #include "gmm_pairaccum.hh"
 
+namespace rasr_gmm {
+
+// the sizes of one set of tables
+struct TableShape {
+    size_t nMeans, nCovs, nEntries, D, slabSlots;
+};
+
+// one set of the f64 accumulators with the later pieces' slab of a call.  The handle holds two: the tables of the
+// maximum-likelihood calls, which are the numerator's, and the denominator's
+struct TableSet {
+    DeviceBuffer<double> meanSums, meanWeights, covSums, covWeights, entryWeights, slabSums, slabWeights;
+    bool                 allocated = false;  // and zeroed: set by the handle
+
+    int alloc(const TableShape& n) {
+        GMM_HIP_CHECK(meanSums.alloc(n.nMeans * n.D));
+        GMM_HIP_CHECK(meanWeights.alloc(n.nMeans));
+        GMM_HIP_CHECK(covSums.alloc(n.nCovs * n.D));
+        GMM_HIP_CHECK(covWeights.alloc(n.nCovs));
+        GMM_HIP_CHECK(entryWeights.alloc(n.nEntries));
+        GMM_HIP_CHECK(slabSums.alloc(n.slabSlots * n.D));
+        GMM_HIP_CHECK(slabWeights.alloc(n.slabSlots));
+        return GMM_OK;
+    }
+    // enqueued on the null stream
+    int zero(const TableShape& n) {
+        if (n.nMeans) {
+            GMM_HIP_CHECK(hipMemset(meanSums.get(), 0, n.nMeans * n.D * sizeof(double)));
+            GMM_HIP_CHECK(hipMemset(meanWeights.get(), 0, n.nMeans * sizeof(double)));
+        }
+        if (n.nCovs) {
+            GMM_HIP_CHECK(hipMemset(covSums.get(), 0, n.nCovs * n.D * sizeof(double)));
+            GMM_HIP_CHECK(hipMemset(covWeights.get(), 0, n.nCovs * sizeof(double)));
+        }
+        if (n.nEntries)
+            GMM_HIP_CHECK(hipMemset(entryWeights.get(), 0, n.nEntries * sizeof(double)));
+        return GMM_OK;
+    }
+    // host copies of the tables a destination is given for; zeros from a set that was never allocated
+    int fetch(const TableShape& n, double* hMeanSums, double* hMeanWeights, double* hCovSums, double* hCovWeights,
+              double* hEntryWeights) const {
+        const struct {
+            double*       dst;
+            const double* src;
+            size_t        n;
+        } copies[5] = {{hMeanSums, meanSums.get(), n.nMeans * n.D},
+                       {hMeanWeights, meanWeights.get(), n.nMeans},
+                       {hCovSums, covSums.get(), n.nCovs * n.D},
+                       {hCovWeights, covWeights.get(), n.nCovs},
+                       {hEntryWeights, entryWeights.get(), n.nEntries}};
+        for (const auto& c : copies)
+            if (c.dst && c.n) {
+                if (allocated)
+                    GMM_HIP_CHECK(hipMemcpy(c.dst, c.src, c.n * sizeof(double), hipMemcpyDeviceToHost));
+                else
+                    std::fill(c.dst, c.dst + c.n, 0.0);
+            }
+        return GMM_OK;
+    }
+};
+
+}  // namespace rasr_gmm
+
 using namespace rasr_gmm;
 
 struct gmm_estimator {
@@ -17,66 +79,36 @@ struct gmm_estimator {
     uint32_t      nMeans = 0, nCovs = 0, nDens = 0;
     // the topology's index tables on the host (serialize)
     std::vector<uint32_t> dnsMean, dnsCov, mixOff, mixDens;
-    // the accumulators
-    DeviceBuffer<double> dMeanSums, dMeanWeights, dCovSums, dCovWeights, dEntryWeights;
-    // scratch of one call of up to maxPairs pairs: the three keys of a pair, the later pieces' slab
+    // the accumulators: side[0] from create; side[1], the denominator's, and the host call's second weight list
+    // (core.dPairWeightDen) are allocated and zeroed by the handle's first discriminative call
+    TableSet side[2];
+    // scratch of one call of up to maxPairs pairs: the three keys of a pair
     DeviceBuffer<uint32_t> dKeyMean, dKeyCov, dKeyEntry;
-    DeviceBuffer<double>   dSlabSums, dSlabWeights;
     // Baum-Welch calls: the posterior rows and the contributions' frames and weights, maxPairs elements each,
-    // allocated by the handle's first posterior call
+    // allocated by the handle's first posterior call; the second weight list by its first joint posterior call
     uint32_t               maxEntries = 1;  // K_max: the largest entry count of a mixture (at least 1)
     bool                   posteriorScratch = false;
     DeviceBuffer<float>    dPostRows;
     DeviceBuffer<uint32_t> dContribFrame;
-    DeviceBuffer<double>   dContribWeight;
-    // discriminative calls: the denominator tables (the numerator's shapes), the second slab and the host call's second
-    // weight list (core.dPairWeightDen), allocated and zeroed by the handle's first discriminative call; the posterior
-    // form's second weight list with the posterior scratch
-    bool                 denominatorTables = false;
-    DeviceBuffer<double> dDenMeanSums, dDenMeanWeights, dDenCovSums, dDenCovWeights, dDenEntryWeights;
-    DeviceBuffer<double> dDenSlabSums, dDenSlabWeights;
-    bool                 denominatorPosteriorScratch = false;
-    DeviceBuffer<double> dContribWeightDen;
-    double               objective = 0.0;  // objectiveFunction_ (host)
+    DeviceBuffer<double>   dContribWeight[2];
+    double                 objective = 0.0;  // objectiveFunction_ (host)
+
+    TableShape shape() const { return {nMeans, nCovs, core.nEntries, core.D, accumSlabSlots(core.maxPairs)}; }
 };
 
 namespace {
 
 constexpr PairNouns kNouns{"estimator", "topology", "estimator topology"};
 
-int zeroDenominatorTables(gmm_estimator* e) {
-    const size_t D = e->core.D;
-    if (e->nMeans) {
-        GMM_HIP_CHECK(hipMemset(e->dDenMeanSums.get(), 0, e->nMeans * D * sizeof(double)));
-        GMM_HIP_CHECK(hipMemset(e->dDenMeanWeights.get(), 0, e->nMeans * sizeof(double)));
-    }
-    if (e->nCovs) {
-        GMM_HIP_CHECK(hipMemset(e->dDenCovSums.get(), 0, e->nCovs * D * sizeof(double)));
-        GMM_HIP_CHECK(hipMemset(e->dDenCovWeights.get(), 0, e->nCovs * sizeof(double)));
-    }
-    if (e->core.nEntries)
-        GMM_HIP_CHECK(hipMemset(e->dDenEntryWeights.get(), 0, e->core.nEntries * sizeof(double)));
-    return GMM_OK;
-}
-
+// both sides, the skipped count and the objective function
 int zeroTables(gmm_estimator* e) {
-    const size_t D = e->core.D;
-    if (e->nMeans) {
-        GMM_HIP_CHECK(hipMemset(e->dMeanSums.get(), 0, e->nMeans * D * sizeof(double)));
-        GMM_HIP_CHECK(hipMemset(e->dMeanWeights.get(), 0, e->nMeans * sizeof(double)));
-    }
-    if (e->nCovs) {
-        GMM_HIP_CHECK(hipMemset(e->dCovSums.get(), 0, e->nCovs * D * sizeof(double)));
-        GMM_HIP_CHECK(hipMemset(e->dCovWeights.get(), 0, e->nCovs * sizeof(double)));
-    }
-    if (e->core.nEntries)
-        GMM_HIP_CHECK(hipMemset(e->dEntryWeights.get(), 0, e->core.nEntries * sizeof(double)));
+    for (TableSet& t : e->side)
+        if (t.allocated) {
+            const int rc = t.zero(e->shape());
+            if (rc != GMM_OK)
+                return rc;
+        }
     GMM_HIP_CHECK(hipMemset(e->core.dSkipped.get(), 0, sizeof(unsigned long long)));
-    if (e->denominatorTables) {
-        const int rc = zeroDenominatorTables(e);
-        if (rc != GMM_OK)
-            return rc;
-    }
     e->objective = 0.0;
     GMM_HIP_CHECK(hipStreamSynchronize(nullptr));  // done before a call on any other stream
     return GMM_OK;
@@ -110,66 +142,74 @@ int create(gmm_estimator* e, const gmm_mixture_set& ms, uint32_t maxPairs, int d
     }
     if ((rc = allocCore(c, topo, false)) != GMM_OK)
         return rc;
-    const size_t D = c.D, P = maxPairs, slots = accumSlabSlots(maxPairs);
-    GMM_HIP_CHECK(e->dMeanSums.alloc(e->nMeans * D));
-    GMM_HIP_CHECK(e->dMeanWeights.alloc(e->nMeans));
-    GMM_HIP_CHECK(e->dCovSums.alloc(e->nCovs * D));
-    GMM_HIP_CHECK(e->dCovWeights.alloc(e->nCovs));
-    GMM_HIP_CHECK(e->dEntryWeights.alloc(c.nEntries));
     for (DeviceBuffer<uint32_t>* b : {&e->dKeyMean, &e->dKeyCov, &e->dKeyEntry})
-        GMM_HIP_CHECK(b->alloc(P));
-    GMM_HIP_CHECK(e->dSlabSums.alloc(slots * D));
-    GMM_HIP_CHECK(e->dSlabWeights.alloc(slots));
+        GMM_HIP_CHECK(b->alloc(maxPairs));
+    if ((rc = e->side[0].alloc(e->shape())) != GMM_OK)
+        return rc;
+    e->side[0].allocated = true;
     return zeroTables(e);
 }
 
 // the three inverted indexes of a call whose keys are written (dKeyMean / dKeyCov / dKeyEntry, dPairIndex = 0, 1, ...):
-// per index the stable sort, the ordered sums of the pieces, the pieces' combination.  n contributions; pairFrame and
-// pairWeight are indexed by contribution
+// per index the stable sort, the ordered sums of the pieces, the pieces' combination, for one side (the tables of
+// side[0]) or two.  n contributions; pairFrame and the weight lists are indexed by contribution (gmm_estimator.hh says
+// what NULL and NaN mean for either side count)
 int accumulateKeyed(gmm_estimator* e, const float* frames, uint32_t frameStride, const uint32_t* pairFrame,
-                    const double* pairWeight, uint32_t nPairs, hipStream_t stream) {
+                    const double* const (&weight)[2], uint32_t sides, uint32_t nPairs, hipStream_t stream) {
     AccumArgs a{};
     a.keysSorted  = e->core.dKeysSorted.get();
     a.indexSorted = e->core.dIndexSorted.get();
     a.pairFrame   = pairFrame;
-    a.pairWeight  = pairWeight;
     a.frames      = frames;
-    a.slabSums    = e->dSlabSums.get();
-    a.slabWeights = e->dSlabWeights.get();
     a.nPairs      = nPairs;
     a.D           = e->core.D;
     a.frameStride = frameStride;
+    a.sides       = sides;
+    for (uint32_t s = 0; s < sides; ++s) {
+        a.weight[s]      = weight[s];
+        a.slabSums[s]    = e->side[s].slabSums.get();
+        a.slabWeights[s] = e->side[s].slabWeights.get();
+    }
     struct Index {
-        const uint32_t* keys;
-        uint32_t        nDest;
-        double *        sums, *weights;
-        int             mode;
+        const uint32_t*      keys;
+        uint32_t             nDest;
+        DeviceBuffer<double> TableSet::*sums, TableSet::*weights;
+        int                  mode;
     };
-    const Index indexes[3] = {{e->dKeyMean.get(), e->nMeans, e->dMeanSums.get(), e->dMeanWeights.get(), kAccumSum},
-                              {e->dKeyCov.get(), e->nCovs, e->dCovSums.get(), e->dCovWeights.get(), kAccumSquare},
-                              {e->dKeyEntry.get(), e->core.nEntries, nullptr, e->dEntryWeights.get(), kAccumWeightOnly}};
+    const Index indexes[3] = {{e->dKeyMean.get(), e->nMeans, &TableSet::meanSums, &TableSet::meanWeights, kAccumSum},
+                              {e->dKeyCov.get(), e->nCovs, &TableSet::covSums, &TableSet::covWeights, kAccumSquare},
+                              {e->dKeyEntry.get(), e->core.nEntries, nullptr, &TableSet::entryWeights, kAccumWeightOnly}};
     for (const Index& x : indexes) {
         if (x.nDest == 0)
             continue;
         GMM_HIP_CHECK(static_cast<hipError_t>(launchAccumSort(e->core.dSortTemp.get(), e->core.sortTempBytes, x.keys, e->core.dPairIndex.get(),
                                                              e->core.dKeysSorted.get(), e->core.dIndexSorted.get(), nPairs,
                                                              keyBits(x.nDest), stream)));
-        a.nDest   = x.nDest;
-        a.sums    = x.sums;
-        a.weights = x.weights;
-        a.mode    = x.mode;
+        a.nDest = x.nDest;
+        a.mode  = x.mode;
+        for (uint32_t s = 0; s < sides; ++s) {
+            a.sums[s]    = x.sums ? (e->side[s].*x.sums).get() : nullptr;
+            a.weights[s] = (e->side[s].*x.weights).get();
+        }
         GMM_HIP_CHECK(static_cast<hipError_t>(launchAccumulateSegments(a, stream)));
         GMM_HIP_CHECK(static_cast<hipError_t>(launchCombinePieces(a, stream)));
     }
     return GMM_OK;
 }
 
-// pass 1 of a Viterbi call: a pair -> the keys of its mean, covariance and mixture entry
-ResolveArgs resolveArgsOf(gmm_estimator* e, const PairCall& call) {
-    ResolveArgs r{};
+// the Viterbi call, one side (weight) or two (weight, weightDen): the best densities where the scorer gives them, a
+// pair -> the keys of its mean, covariance and mixture entry, then the keyed tail
+int accumulateOn(gmm_estimator* e, gmm_scorer* scorer, PairCall call, uint32_t sides, hipStream_t stream) {
+    const int rc = bestDensities(e->core, scorer, call, stream);  // the Viterbi branch
+    if (rc != GMM_OK)
+        return rc;
+    const double* const weight[2] = {call.weight, call.weightDen};
+    ResolveArgs         r{};
     r.pairFrame   = call.pairFrame;
     r.pairMix     = call.pairMix;
     r.pairDensity = call.pairDensity;
+    r.weight[0]   = weight[0];
+    r.weight[1]   = weight[1];
     r.mixOff      = e->core.dMixOff.get();
     r.entryMean   = e->core.dEntryMean.get();
     r.entryCov    = e->core.dEntryCov.get();
@@ -184,15 +224,9 @@ ResolveArgs resolveArgsOf(gmm_estimator* e, const PairCall& call) {
     r.nMeans      = e->nMeans;
     r.nCovs       = e->nCovs;
     r.nEntries    = e->core.nEntries;
-    return r;
-}
-
-int accumulateOn(gmm_estimator* e, gmm_scorer* scorer, PairCall call, hipStream_t stream) {
-    const int rc = bestDensities(e->core, scorer, call, stream);  // the Viterbi branch
-    if (rc != GMM_OK)
-        return rc;
-    GMM_HIP_CHECK(static_cast<hipError_t>(launchResolvePairs(resolveArgsOf(e, call), stream)));
-    return accumulateKeyed(e, call.frames, call.frameStride, call.pairFrame, call.weight, call.nPairs, stream);
+    r.sides       = sides;
+    GMM_HIP_CHECK(static_cast<hipError_t>(launchResolvePairs(r, stream)));
+    return accumulateKeyed(e, call.frames, call.frameStride, call.pairFrame, weight, sides, call.nPairs, stream);
 }
 
 // the checks of a posterior call that need no device: checkPairCall's, diagonal-sum only, contribution slots
@@ -218,7 +252,7 @@ int ensurePosteriorScratch(gmm_estimator* e) {
         return GMM_OK;
     GMM_HIP_CHECK(e->dPostRows.alloc(e->core.maxPairs));
     GMM_HIP_CHECK(e->dContribFrame.alloc(e->core.maxPairs));
-    GMM_HIP_CHECK(e->dContribWeight.alloc(e->core.maxPairs));
+    GMM_HIP_CHECK(e->dContribWeight[0].alloc(e->core.maxPairs));
     e->posteriorScratch = true;
     return GMM_OK;
 }
@@ -248,111 +282,35 @@ int accumulatePosteriorsOn(gmm_estimator* e, gmm_scorer* scorer, const PairCall&
     q.keyEntry       = e->dKeyEntry.get();
     q.contribIndex   = e->core.dPairIndex.get();
     q.contribFrame   = e->dContribFrame.get();
-    q.contribWeight  = e->dContribWeight.get();
+    q.contribWeight  = e->dContribWeight[0].get();
     q.skipped        = e->core.dSkipped.get();
     q.nMeans         = e->nMeans;
     q.nCovs          = e->nCovs;
     q.nEntries       = e->core.nEntries;
     GMM_HIP_CHECK(scorer ? launchDensityPosteriors(q, stream) : launchExpandSingleDensity(q, stream));
-    return accumulateKeyed(e, call.frames, call.frameStride, e->dContribFrame.get(), e->dContribWeight.get(),
-                           call.nPairs * q.rowStride, stream);
+    return accumulateKeyed(e, call.frames, call.frameStride, e->dContribFrame.get(), {e->dContribWeight[0].get(), nullptr},
+                           1, call.nPairs * q.rowStride, stream);
 }
 
-// the denominator tables and the second slab, on the handle's first discriminative call
+// the denominator tables with their slab and the host call's second weight list, on the handle's first discriminative
+// call
 int ensureDenominatorTables(gmm_estimator* e) {
-    if (e->denominatorTables)
+    TableSet& den = e->side[1];
+    if (den.allocated)
         return GMM_OK;
-    const size_t D = e->core.D, slots = accumSlabSlots(e->core.maxPairs);
-    GMM_HIP_CHECK(e->dDenMeanSums.alloc(e->nMeans * D));
-    GMM_HIP_CHECK(e->dDenMeanWeights.alloc(e->nMeans));
-    GMM_HIP_CHECK(e->dDenCovSums.alloc(e->nCovs * D));
-    GMM_HIP_CHECK(e->dDenCovWeights.alloc(e->nCovs));
-    GMM_HIP_CHECK(e->dDenEntryWeights.alloc(e->core.nEntries));
-    GMM_HIP_CHECK(e->dDenSlabSums.alloc(slots * D));
-    GMM_HIP_CHECK(e->dDenSlabWeights.alloc(slots));
-    GMM_HIP_CHECK(e->core.dPairWeightDen.alloc(e->core.maxPairs));
-    const int rc = zeroDenominatorTables(e);
+    int rc = den.alloc(e->shape());
     if (rc != GMM_OK)
+        return rc;
+    GMM_HIP_CHECK(e->core.dPairWeightDen.alloc(e->core.maxPairs));
+    if ((rc = den.zero(e->shape())) != GMM_OK)
         return rc;
     GMM_HIP_CHECK(hipStreamSynchronize(nullptr));  // done before the call on any other stream
-    e->denominatorTables = true;
+    den.allocated = true;
     return GMM_OK;
-}
-
-int ensureDenominatorPosteriorScratch(gmm_estimator* e) {
-    if (e->denominatorPosteriorScratch)
-        return GMM_OK;
-    GMM_HIP_CHECK(e->dContribWeightDen.alloc(e->core.maxPairs));
-    e->denominatorPosteriorScratch = true;
-    return GMM_OK;
-}
-
-// accumulateKeyed with two accumulators per destination (gmm_kernels_accum_dual.hip): the same three sorts, once.
-// weightNum / weightDen are indexed by contribution, NaN where the contribution is not live on the side, NULL for a
-// side that receives nothing
-int accumulateKeyedDual(gmm_estimator* e, const float* frames, uint32_t frameStride, const uint32_t* pairFrame,
-                        const double* weightNum, const double* weightDen, uint32_t nPairs, hipStream_t stream) {
-    DualAccumArgs a{};
-    a.keysSorted     = e->core.dKeysSorted.get();
-    a.indexSorted    = e->core.dIndexSorted.get();
-    a.pairFrame      = pairFrame;
-    a.frames         = frames;
-    a.weight[0]      = weightNum;
-    a.weight[1]      = weightDen;
-    a.slabSums[0]    = e->dSlabSums.get();
-    a.slabSums[1]    = e->dDenSlabSums.get();
-    a.slabWeights[0] = e->dSlabWeights.get();
-    a.slabWeights[1] = e->dDenSlabWeights.get();
-    a.nPairs         = nPairs;
-    a.D              = e->core.D;
-    a.frameStride    = frameStride;
-    struct Index {
-        const uint32_t* keys;
-        uint32_t        nDest;
-        double *        sums, *weights, *denSums, *denWeights;
-        int             mode;
-    };
-    const Index indexes[3] = {
-            {e->dKeyMean.get(), e->nMeans, e->dMeanSums.get(), e->dMeanWeights.get(), e->dDenMeanSums.get(),
-             e->dDenMeanWeights.get(), kAccumSum},
-            {e->dKeyCov.get(), e->nCovs, e->dCovSums.get(), e->dCovWeights.get(), e->dDenCovSums.get(),
-             e->dDenCovWeights.get(), kAccumSquare},
-            {e->dKeyEntry.get(), e->core.nEntries, nullptr, e->dEntryWeights.get(), nullptr, e->dDenEntryWeights.get(),
-             kAccumWeightOnly}};
-    for (const Index& x : indexes) {
-        if (x.nDest == 0)
-            continue;
-        GMM_HIP_CHECK(static_cast<hipError_t>(launchAccumSort(e->core.dSortTemp.get(), e->core.sortTempBytes, x.keys, e->core.dPairIndex.get(),
-                                                             e->core.dKeysSorted.get(), e->core.dIndexSorted.get(), nPairs,
-                                                             keyBits(x.nDest), stream)));
-        a.nDest      = x.nDest;
-        a.sums[0]    = x.sums;
-        a.sums[1]    = x.denSums;
-        a.weights[0] = x.weights;
-        a.weights[1] = x.denWeights;
-        a.mode       = x.mode;
-        GMM_HIP_CHECK(static_cast<hipError_t>(launchAccumulateSegmentsDual(a, stream)));
-        GMM_HIP_CHECK(static_cast<hipError_t>(launchCombinePiecesDual(a, stream)));
-    }
-    return GMM_OK;
-}
-
-// the joint Viterbi call: accumulateOn with two weight lists
-int accumulateDiscriminativeOn(gmm_estimator* e, gmm_scorer* scorer, PairCall call, hipStream_t stream) {
-    const int rc = bestDensities(e->core, scorer, call, stream);  // the Viterbi branch
-    if (rc != GMM_OK)
-        return rc;
-    DualResolveArgs q{};
-    q.r         = resolveArgsOf(e, call);
-    q.weightNum = call.weight;
-    q.weightDen = call.weightDen;
-    GMM_HIP_CHECK(static_cast<hipError_t>(launchResolvePairsDual(q, stream)));
-    return accumulateKeyedDual(e, call.frames, call.frameStride, call.pairFrame, call.weight, call.weightDen, call.nPairs,
-                               stream);
 }
 
 // the joint Baum-Welch call: the posterior rows once (the kernel of gmm_density_posteriors_pairs_device), their
-// expansion into contribution slots with one finalWeight per side, then the dual keyed tail
+// expansion into contribution slots with one finalWeight per side, then the keyed tail for two sides
 int accumulateDiscriminativePosteriorsOn(gmm_estimator* e, gmm_scorer* scorer, const PairCall& call,
                                          double threshold, hipStream_t stream) {
     const uint32_t rowStride = scorer ? e->maxEntries : 1u;
@@ -366,11 +324,11 @@ int accumulateDiscriminativePosteriorsOn(gmm_estimator* e, gmm_scorer* scorer, c
         q.rowStride      = rowStride;
         GMM_HIP_CHECK(launchDensityPosteriors(q, stream));
     }
-    DualExpandArgs x{};
+    ExpandArgs x{};
     x.pairFrame        = call.pairFrame;
     x.pairMix          = call.pairMix;
-    x.weightNum        = call.weight;
-    x.weightDen        = call.weightDen;
+    x.weight[0]        = call.weight;
+    x.weight[1]        = call.weightDen;
     x.posteriors       = scorer ? e->dPostRows.get() : nullptr;
     x.mixOff           = e->core.dMixOff.get();
     x.entryMean        = e->core.dEntryMean.get();
@@ -380,8 +338,8 @@ int accumulateDiscriminativePosteriorsOn(gmm_estimator* e, gmm_scorer* scorer, c
     x.keyEntry         = e->dKeyEntry.get();
     x.contribIndex     = e->core.dPairIndex.get();
     x.contribFrame     = e->dContribFrame.get();
-    x.contribWeightNum = e->dContribWeight.get();
-    x.contribWeightDen = e->dContribWeightDen.get();
+    x.contribWeight[0] = e->dContribWeight[0].get();
+    x.contribWeight[1] = e->dContribWeight[1].get();
     x.skipped          = e->core.dSkipped.get();
     x.threshold        = threshold;
     x.nPairs           = call.nPairs;
@@ -391,10 +349,11 @@ int accumulateDiscriminativePosteriorsOn(gmm_estimator* e, gmm_scorer* scorer, c
     x.nMeans           = e->nMeans;
     x.nCovs            = e->nCovs;
     x.nEntries         = e->core.nEntries;
-    GMM_HIP_CHECK(static_cast<hipError_t>(launchExpandDual(x, stream)));
-    return accumulateKeyedDual(e, call.frames, call.frameStride, e->dContribFrame.get(),
-                               call.weight ? e->dContribWeight.get() : nullptr,
-                               call.weightDen ? e->dContribWeightDen.get() : nullptr, call.nPairs * rowStride, stream);
+    GMM_HIP_CHECK(static_cast<hipError_t>(launchExpandPosteriorRows(x, stream)));
+    return accumulateKeyed(e, call.frames, call.frameStride, e->dContribFrame.get(),
+                           {call.weight ? e->dContribWeight[0].get() : nullptr,
+                            call.weightDen ? e->dContribWeight[1].get() : nullptr},
+                           2, call.nPairs * rowStride, stream);
 }
 
 // what a joint Baum-Welch call needs: the denominator tables even for a call of no pairs, the scratch for one with pairs
@@ -404,7 +363,9 @@ int ensureDiscriminativePosteriors(gmm_estimator* e, uint32_t nPairs) {
         return rc;
     if ((rc = ensurePosteriorScratch(e)) != GMM_OK)
         return rc;
-    return ensureDenominatorPosteriorScratch(e);
+    if (!e->dContribWeight[1].get())
+        GMM_HIP_CHECK(e->dContribWeight[1].alloc(e->core.maxPairs));
+    return GMM_OK;
 }
 
 // the check of a discriminative call that needs no device
@@ -414,62 +375,28 @@ int checkSides(const double* weightNum, const double* weightDen) {
     return GMM_OK;
 }
 
-// host copies of the tables, after the last call
+// host copies of a side's tables, after the last call
 struct HostTables {
     std::vector<double> meanSums, meanWeights, covSums, covWeights, entryWeights;
+    explicit HostTables(const TableShape& n)
+        : meanSums(n.nMeans * n.D), meanWeights(n.nMeans), covSums(n.nCovs * n.D), covWeights(n.nCovs), entryWeights(n.nEntries) {}
 };
-int fetch(gmm_estimator* e, double* meanSums, double* meanWeights, double* covSums, double* covWeights, double* entryWeights) {
+// side 1: zeros for a handle that has seen no discriminative call (the tables are not allocated then)
+int fetch(gmm_estimator* e, int side, double* meanSums, double* meanWeights, double* covSums, double* covWeights,
+          double* entryWeights) {
     GMM_HIP_CHECK(hipSetDevice(e->core.device));
     const int rc = waitDone(e->core);
     if (rc != GMM_OK)
         return rc;
-    const size_t D = e->core.D;
-    const struct {
-        double*       dst;
-        const double* src;
-        size_t        n;
-    } copies[5] = {{meanSums, e->dMeanSums.get(), e->nMeans * D},    {meanWeights, e->dMeanWeights.get(), e->nMeans},
-                   {covSums, e->dCovSums.get(), e->nCovs * D},       {covWeights, e->dCovWeights.get(), e->nCovs},
-                   {entryWeights, e->dEntryWeights.get(), e->core.nEntries}};
-    for (const auto& c : copies)
-        if (c.dst && c.n)
-            GMM_HIP_CHECK(hipMemcpy(c.dst, c.src, c.n * sizeof(double), hipMemcpyDeviceToHost));
-    return GMM_OK;
+    return e->side[side].fetch(e->shape(), meanSums, meanWeights, covSums, covWeights, entryWeights);
 }
-
-// the denominator tables; zeros for a handle that has seen no discriminative call (they are not allocated then)
-int fetchDenominator(gmm_estimator* e, double* meanSums, double* meanWeights, double* covSums, double* covWeights,
-                     double* entryWeights) {
-    GMM_HIP_CHECK(hipSetDevice(e->core.device));
-    const int rc = waitDone(e->core);
-    if (rc != GMM_OK)
-        return rc;
-    const size_t D = e->core.D;
-    const struct {
-        double*       dst;
-        const double* src;
-        size_t        n;
-    } copies[5] = {{meanSums, e->dDenMeanSums.get(), e->nMeans * D}, {meanWeights, e->dDenMeanWeights.get(), e->nMeans},
-                   {covSums, e->dDenCovSums.get(), e->nCovs * D},    {covWeights, e->dDenCovWeights.get(), e->nCovs},
-                   {entryWeights, e->dDenEntryWeights.get(), e->core.nEntries}};
-    for (const auto& c : copies)
-        if (c.dst && c.n) {
-            if (e->denominatorTables)
-                GMM_HIP_CHECK(hipMemcpy(c.dst, c.src, c.n * sizeof(double), hipMemcpyDeviceToHost));
-            else
-                std::fill(c.dst, c.dst + c.n, 0.0);
-        }
-    return GMM_OK;
+int fetch(gmm_estimator* e, int side, HostTables& h) {
+    return fetch(e, side, h.meanSums.data(), h.meanWeights.data(), h.covSums.data(), h.covWeights.data(), h.entryWeights.data());
 }
 
 int serialize(gmm_estimator* e, std::vector<unsigned char>& bytes, bool discriminative = false) {
-    HostTables h;
-    h.meanSums.resize(static_cast<size_t>(e->nMeans) * e->core.D);
-    h.meanWeights.resize(e->nMeans);
-    h.covSums.resize(static_cast<size_t>(e->nCovs) * e->core.D);
-    h.covWeights.resize(e->nCovs);
-    h.entryWeights.resize(e->core.nEntries);
-    const int rc = fetch(e, h.meanSums.data(), h.meanWeights.data(), h.covSums.data(), h.covWeights.data(), h.entryWeights.data());
+    HostTables h(e->shape());
+    const int  rc = fetch(e, 0, h);
     if (rc != GMM_OK)
         return rc;
     EstimatorTables t{};
@@ -491,14 +418,8 @@ int serialize(gmm_estimator* e, std::vector<unsigned char>& bytes, bool discrimi
         bytes = writeEstimatorFile(t);
         return GMM_OK;
     }
-    HostTables d;
-    d.meanSums.resize(h.meanSums.size());
-    d.meanWeights.resize(h.meanWeights.size());
-    d.covSums.resize(h.covSums.size());
-    d.covWeights.resize(h.covWeights.size());
-    d.entryWeights.resize(h.entryWeights.size());
-    const int rd = fetchDenominator(e, d.meanSums.data(), d.meanWeights.data(), d.covSums.data(), d.covWeights.data(),
-                                    d.entryWeights.data());
+    HostTables d(e->shape());
+    const int  rd = fetch(e, 1, d);
     if (rd != GMM_OK)
         return rd;
     DenominatorTables den{};
@@ -577,7 +498,7 @@ int gmm_estimator_accumulate_device(gmm_estimator* e, gmm_scorer* scorer, const 
     if (rc != GMM_OK || nPairs == 0)
         return rc;
     return deviceCall(e->core, nPairs, stream, nothingToPrepare,
-                      [&](hipStream_t st) { return accumulateOn(e, scorer, call, st); });
+                      [&](hipStream_t st) { return accumulateOn(e, scorer, call, 1, st); });
 }
 
 int gmm_estimator_accumulate_host(gmm_estimator* e, gmm_scorer* scorer, const float* frames, uint32_t nFrames,
@@ -588,7 +509,7 @@ int gmm_estimator_accumulate_host(gmm_estimator* e, gmm_scorer* scorer, const fl
     if (rc != GMM_OK || nPairs == 0)
         return rc;
     return hostCall(e->core, call, nothingToPrepare,
-                    [&](const PairCall& staged) { return accumulateOn(e, scorer, staged, nullptr); });
+                    [&](const PairCall& staged) { return accumulateOn(e, scorer, staged, 1, nullptr); });
 }
 
 int gmm_estimator_accumulate_posteriors_device(gmm_estimator* e, gmm_scorer* scorer, const float* frames, uint32_t nFrames,
@@ -626,7 +547,7 @@ int gmm_estimator_accumulate_discriminative_device(gmm_estimator* e, gmm_scorer*
     if (rc != GMM_OK)
         return rc;
     return deviceCall(e->core, nPairs, stream, [&] { return ensureDenominatorTables(e); },
-                      [&](hipStream_t st) { return accumulateDiscriminativeOn(e, scorer, call, st); });
+                      [&](hipStream_t st) { return accumulateOn(e, scorer, call, 2, st); });
 }
 
 int gmm_estimator_accumulate_discriminative_host(gmm_estimator* e, gmm_scorer* scorer, const float* frames,
@@ -640,7 +561,7 @@ int gmm_estimator_accumulate_discriminative_host(gmm_estimator* e, gmm_scorer* s
     if (rc != GMM_OK)
         return rc;
     return hostCall(e->core, call, [&] { return ensureDenominatorTables(e); },
-                    [&](const PairCall& staged) { return accumulateDiscriminativeOn(e, scorer, staged, nullptr); });
+                    [&](const PairCall& staged) { return accumulateOn(e, scorer, staged, 2, nullptr); });
 }
 
 int gmm_estimator_accumulate_discriminative_posteriors_device(gmm_estimator* e, gmm_scorer* scorer, const float* frames,
@@ -693,7 +614,7 @@ int gmm_estimator_get_denominator(gmm_estimator* e, double* meanSums, double* me
                                   double* covWeights, double* entryWeights) {
     if (!e)
         return fail(GMM_ERR_INVALID_ARGUMENT, "null estimator");
-    return fetchDenominator(e, meanSums, meanWeights, covSums, covWeights, entryWeights);
+    return fetch(e, 1, meanSums, meanWeights, covSums, covWeights, entryWeights);
 }
 
 int gmm_estimator_serialize_discriminative(gmm_estimator* e, void* data, uint64_t capacity, uint64_t* size) {
@@ -731,7 +652,7 @@ int gmm_estimator_get(gmm_estimator* e, double* meanSums, double* meanWeights, d
                       double* entryWeights) {
     if (!e)
         return fail(GMM_ERR_INVALID_ARGUMENT, "null estimator");
-    return fetch(e, meanSums, meanWeights, covSums, covWeights, entryWeights);
+    return fetch(e, 0, meanSums, meanWeights, covSums, covWeights, entryWeights);
 }
 
 int gmm_estimator_serialize(gmm_estimator* e, void* data, uint64_t capacity, uint64_t* size) {

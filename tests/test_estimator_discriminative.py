@@ -1,5 +1,5 @@
 """Joint numerator / denominator accumulation for discriminative training on the device:
-gmm_estimator_accumulate_discriminative_* (rasr_amd/csrc/gmm_kernels_accum_dual.hip, include/rasr_gmm_estimator.h
+gmm_estimator_accumulate_discriminative_* (rasr_amd/csrc/gmm_kernels_accum.hip with two sides, include/rasr_gmm_estimator.h
 "Discriminative training"), against the plain-numpy restatement of the contract in tests/ebw_restatement.py.
 
 Everything is compared bit for bit: both sides run the same IEEE f64 operations in the same order.  The only
@@ -216,6 +216,76 @@ def test_pieces(gpu, n):
         wbound = 2.0 * live * 2.0 ** -53 * np.abs(w[~np.isnan(w)]).sum()
         assert abs(got["covariance_weights"][0] - seq["covariance_weights"][0]) <= wbound
         print(f"n = {n}: max |joint - sequential| = {worst:.3f} of the bound")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# one kernel family, two meanings of a weight: the maximum-likelihood call's and the joint call's
+# ---------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dim", [1, 65])  # 65: a second lane block
+def test_nan_weight_keeps_its_two_meanings(gpu, dim):
+    """A NaN weight is a value to the maximum-likelihood call (it poisons its destinations) and "not live" to the joint
+    call (nothing is added).  513 pairs on one mean, so two pieces and a combine; the NaN pair sits in the second."""
+    ms = ra.synthetic_mixture_set(6, COUNTS, dim, seed=40 + dim)  # one covariance: every pair lands on it
+    F = 32
+    frames = ra.synthetic_frames(F, dim, seed=17)
+    rng = np.random.default_rng(41 + dim)
+    # entry 0 (mixture 0, density 0) takes 513 pairs; six pairs of other entries in between
+    others = {3: (1, 2), 100: (2, 0), 300: (3, 1), 400: (1, 0), 515: (5, 1), 517: (4, 0)}
+    n = 513 + len(others)
+    pm, pd = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+    for at, (m, d) in others.items():
+        pm[at], pd[at] = m, d
+    pf = rng.integers(0, F, n).astype(np.uint32)
+    w = rng.uniform(0.5, 2, n)
+    ent = entries_of(ms, pm, pd)
+    mean_of = ms.density_mean[ms.mixture_densities[ent]].astype(np.int64)
+    heavy = np.flatnonzero(ent == 0)
+    assert len(heavy) == 513 and (mean_of[ent != 0] != mean_of[0]).all() and ms.n_covariances == 1
+    bad = heavy[-1]  # the 513th pair of its mean and of its entry, and in the second piece of the covariance
+    assert bad >= 512
+    w[bad] = NAN
+    z = er.zero_tables(ms)
+
+    e = ra.Estimator(ms, n)
+    assert ml(gpu, e, frames, pf, pm, pd, w) == 0
+    got = e.get()
+    seq = er.sequential(ms, frames, ent, pf, w, z)  # the live rows: right wherever the NaN pair does not land
+    hit = {"mean_sums": mean_of[0], "mean_weights": mean_of[0], "covariance_sums": 0, "covariance_weights": 0,
+           "entry_weights": 0}
+    for key in KEYS:
+        poisoned = np.zeros(len(got[key]), dtype=bool)
+        poisoned[hit[key]] = True
+        assert np.isnan(got[key][poisoned]).all(), key
+        assert np.array_equal(got[key][~poisoned].view(np.uint64), seq[key][~poisoned].view(np.uint64)), key
+
+    j = ra.Estimator(ms, n)
+    assert disc(gpu, j, frames, pf, pm, pd, w, None) == 0
+    keep = np.arange(n) != bad
+    want = er.joint(ms, frames, ent[keep], pf[keep], w[keep], None, z, z)[0]
+    got = j.get()
+    assert same(got, want) and not any(np.isnan(got[k]).any() for k in KEYS)
+    assert same(j.get_denominator(), z)
+
+
+@pytest.mark.parametrize("n", [513, 1600])
+def test_one_sided_joint_call_is_a_maximum_likelihood_call(gpu, n):
+    """With one side and no absent pair the joint piece cut is the side's own cut: bit-equal beyond 512 too."""
+    ms = ra.synthetic_mixture_set(6, COUNTS, 39, seed=6)
+    F = 64
+    frames = ra.synthetic_frames(F, 39, seed=13)
+    pf, pm, pd, w, _ = viterbi_case(ms, n, F, 2000 + n, absent=False)
+    ref = ra.Estimator(ms, n)
+    assert ml(gpu, ref, frames, pf, pm, pd, w) == 0
+    want = ref.get()
+    assert want["covariance_weights"][0] != 0
+    z = er.zero_tables(ms)
+    num = ra.Estimator(ms, n)
+    assert disc(gpu, num, frames, pf, pm, pd, w, None) == 0
+    assert same(num.get(), want) and same(num.get_denominator(), z)
+    den = ra.Estimator(ms, n)
+    assert disc(gpu, den, frames, pf, pm, pd, None, w) == 0
+    assert same(den.get_denominator(), want) and same(den.get(), z)
 
 
 # ---------------------------------------------------------------------------------------------------------------
