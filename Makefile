@@ -31,7 +31,7 @@ OBJS      = $(BUILD)/gmm_kernels_i8.o $(BUILD)/gmm_kernels_f32.o $(BUILD)/gmm_ke
             $(BUILD)/gmm_kernels_keyed.o $(BUILD)/gmm_pairaccum.o $(BUILD)/PairTopology.o \
             $(BUILD)/gmm_kernels_adapt.o $(BUILD)/gmm_adapt.o $(BUILD)/AffineTransformEstimate.o \
             $(BUILD)/gmm_kernels_mllr.o $(BUILD)/gmm_mllr.o $(BUILD)/MllrEstimate.o \
-            $(BUILD)/gmm_kernels_align.o $(BUILD)/gmm_align.o $(BUILD)/AlignGraph.o
+            $(BUILD)/gmm_kernels_align.o $(BUILD)/gmm_kernels_align_posterior.o $(BUILD)/gmm_align.o $(BUILD)/AlignGraph.o
 # the core of the handles that accumulate pairs (gmm_pairaccum.hh names the chunk constants of both adaptation headers)
 PAIR_HDRS = $(SRC)/gmm_pairaccum.hh $(SRC)/host/PairTopology.hh $(SRC)/gmm_estimator.hh include/rasr_gmm_estimator.h \
             include/rasr_gmm_adaptation.h include/rasr_gmm_mllr.h
@@ -53,8 +53,9 @@ EBWEST   = $(BUILD)/tests/ebw_estimate_test
 MLLREST  = $(BUILD)/tests/mllr_estimate_test
 PAIRTOPO = $(BUILD)/tests/pair_topology_test
 ALIGNGRAPH = $(BUILD)/tests/align_graph_test
+ALIGNPOSTGRAPH = $(BUILD)/tests/align_posterior_graph_test
 
-all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) $(EBWEST) $(MLLREST) $(PAIRTOPO) $(ALIGNGRAPH) oracle reference-scorers check-integration
+all: $(LIB) $(DRIVER) $(REFSORT) $(CLASSLAYOUT) $(ESTCOMBINE) $(AFFINEEST) $(EBWEST) $(MLLREST) $(PAIRTOPO) $(ALIGNGRAPH) $(ALIGNPOSTGRAPH) oracle reference-scorers check-integration
 
 $(BUILD)/gmm_kernels_i8.o: $(SRC)/gmm_kernels_i8.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -152,6 +153,12 @@ $(BUILD)/MllrEstimate.o: $(SRC)/host/MllrEstimate.cc include/rasr_gmm.h include/
 # Viterbi alignment over a score table (gmm_aligner_*): one workgroup per segment, f32 additions and comparisons only,
 # every one an _rn intrinsic.  Not one of KERNEL_OBJS
 $(BUILD)/gmm_kernels_align.o: $(SRC)/gmm_kernels_align.hip $(ALIGN_HDRS)
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# Baum-Welch alignment (gmm_aligner_posteriors_*): the f32 search, the f64 potentials and the per-frame items, every
+# add, subtract, multiply and divide an _rn intrinsic; exp and log1p are the device library's f64 functions
+$(BUILD)/gmm_kernels_align_posterior.o: $(SRC)/gmm_kernels_align_posterior.hip $(ALIGN_HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -289,6 +296,19 @@ $(ALIGNGRAPH)_san: $(ALIGNGRAPH_DEPS)
 check-align-graph: $(ALIGNGRAPH)_san
 	$(ALIGNGRAPH)_san
 
+# host check of the mixture groups and the column order that the Baum-Welch call reads (no GPU, no HIP)
+ALIGNPOSTGRAPH_SRCS = tests/cpp/align_posterior_graph_test.cc $(SRC)/host/AlignGraph.cc
+ALIGNPOSTGRAPH_DEPS = $(ALIGNPOSTGRAPH_SRCS) $(SRC)/host/AlignGraph.hh include/rasr_gmm.h include/rasr_gmm_align.h
+$(ALIGNPOSTGRAPH): $(ALIGNPOSTGRAPH_DEPS)
+	@mkdir -p $(BUILD)/tests
+	g++ $(HOSTFLAGS) -o $@ $(ALIGNPOSTGRAPH_SRCS)
+	$@
+$(ALIGNPOSTGRAPH)_san: $(ALIGNPOSTGRAPH_DEPS)
+	@mkdir -p $(BUILD)/tests
+	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(ALIGNPOSTGRAPH_SRCS)
+check-align-posterior-graph: $(ALIGNPOSTGRAPH)_san
+	$(ALIGNPOSTGRAPH)_san
+
 $(DRIVER): tests/cpp/feature_scorer_driver.cc $(LIB) $(HDRS)
 	@mkdir -p $(BUILD)/tests
 	g++ $(HOSTFLAGS) -o $@ $< -L$(LIBDIR) -lrasr_gmm -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
@@ -381,4 +401,4 @@ clean:
 print-%:
 	@echo '$($*)'
 
-.PHONY: all oracle reference-scorers clean check-integration check-integration-link check-align-graph
+.PHONY: all oracle reference-scorers clean check-integration check-integration-link check-align-graph check-align-posterior-graph

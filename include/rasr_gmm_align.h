@@ -13,7 +13,8 @@
  *   Aligner::feed(Scorer)                                         src/Search/Aligner.cc:585-592
  *   Aligner::SearchSpace::finalStatePotential                     src/Search/Aligner.cc:376-396
  *   Aligner::SearchSpace::getAlignmentFsaViterbi                  src/Search/Aligner.cc:398-436
- * Not covered: Baum-Welch mode (the arc posteriors), n-best pruning, the threshold-increase loop of
+ * Baum-Welch mode (the per-frame mixture posteriors) is gmm_aligner_posteriors_*, described further down.
+ * Not covered: n-best pruning, the threshold-increase loop of
  * feed(vector) -- out_score and out_hypotheses are what a caller needs to run it --, per-frame local scores, building
  * the automata from a lexicon or from allophone states, word lattices, a RASR-side adapter.
  *
@@ -65,6 +66,11 @@ extern "C" {
  * state) in LDS, double-buffered over the frames: 10 bytes per state out of the 64 KiB a workgroup takes without asking
  * for more, 4 KiB of which stay free for the reductions.  (64 KiB - 4 KiB) / 10 = 6144. */
 #define GMM_ALIGN_MAX_STATES 6144
+
+/* The most states of a segment in a Baum-Welch (posteriors) call.  Its workgroup keeps two f64 potential rows beside the
+ * two f32 score rows and the two rows of marks: 26 bytes per state, in rows rounded up to 64 states, out of the same
+ * 64 KiB, 1 KiB of which stays free for the reductions.  (64 KiB - 1 KiB) / 26 = 2481, in whole rows of 64: 2432. */
+#define GMM_ALIGN_MAX_STATES_POSTERIOR 2432
 
 /* The most arcs that may enter one state: a backpointer keeps the arc's ordinal in the state's incoming list in 16
  * bits. */
@@ -133,6 +139,91 @@ int gmm_aligner_align_device(gmm_aligner* aligner, const float* scores, uint32_t
 int gmm_aligner_align_host(gmm_aligner* aligner, const float* scores, uint32_t n_table_frames, uint32_t score_stride,
                            float pruning_threshold, uint32_t* out_mixture, uint32_t* out_state, uint32_t* out_arc,
                            float* out_score, uint32_t* out_hypotheses);
+
+/*
+ * BAUM-WELCH MODE: per-frame mixture posteriors of the batch set by gmm_aligner_set_segments.  Replaces Search::Aligner
+ * in baum-welch mode with acoustic pruning, up to the normalised alignment items:
+ *   Aligner::SearchSpace::activateOrUpdateStateHypothesisBaumWelch, expand, prune   src/Search/Aligner.cc:160-187, 206-309
+ *   Aligner::SearchSpace::finalStatePotential, getAlignmentFsaBaumWelch             src/Search/Aligner.cc:376-396, 438-452
+ *   Aligner::getAlignment, getAlignmentPosteriorFsa                                 src/Search/Aligner.cc:696-779
+ *   Fsa::posterior64                                                                src/Fsa/Sssp.cc:67-222
+ *   LogSemiring::collect                                                            src/Fsa/tRealSemiring.cc:130-146
+ *   Alignment::combineItems .. filterWeightsGT                                      src/Speech/Alignment.cc:442-578
+ * Not covered: use-partial-sums, a positive min-weight (the arc-level prunePosterior), n-best pruning, the
+ * threshold-increase loop of feed(vector), gamma scaling, the state-posteriors statistics channel, a RASR-side adapter.
+ *
+ * THE NUMERIC CONTRACT of this mode.  Every f32 or f64 add, subtract, multiply and divide is one correctly rounded
+ * operation, nothing is contracted; every exp and log1p is evaluated in f64 on the exactly widened argument and, in an
+ * f32 step, its value is rounded once to f32.  The result is the same bit for bit for every batch composition, launch
+ * geometry and run (no floating-point atomics).  Defined for finite table entries, arc weights and final weights (+inf
+ * as a final weight: not final); for other inputs the result is unspecified, the call stays in bounds and terminates.
+ *   collect(a, b)  f32: b == FLT_MAX -> a; a == FLT_MAX -> b; else with lo = min(a, b), hi = max(a, b):
+ *                  lo - f32(log1p(exp(f64(lo - hi))))          (FLT_MAX is the log semiring's zero)
+ *   1 search   f32.  Start as in Viterbi mode.  Frame t, state q: over the incoming arcs (p -> q, m, w) from the states p
+ *              active after frame t-1, in (p ascending, arc position ascending) order:
+ *                  arcScore = w + table[m][frame_begin + t];   cand = score(p) + arcScore
+ *              the first candidate initialises score(q), a later one gives score(q) = collect(score(q), cand).
+ *              prune: exactly Viterbi mode's, on these scores; so is the hypothesis count.
+ *              end: result = FLT_MAX; for the active q with a final weight below +inf, ascending: v = final_weight(q) +
+ *              score(q); result = (result == FLT_MAX) ? v : collect(result, v).  The segment HAS AN ALIGNMENT iff there is
+ *              such a q; otherwise it has no items, out_score = FLT_MAX and out_log_total = DBL_MAX.
+ *   2 trellis  nodes: the initial state before frame 0 and every (t, q) with q active after frame t; arcs: (t-1, p) ->
+ *              (t, q) for every arc p -> q with both ends nodes, with the f32 weight arcScore.
+ *   3 potentials, f64, zero = DBL_MAX.  extend(x, s) = x + f64(s), an infinity replaced by DBL_MAX.  The batch form over
+ *              values v_1 .. v_k in a stated order: min = DBL_MAX, and for i = 1 .. k: if (v_i <= min) min = v_i, i* = i;
+ *              sum = 0, and for i != i*, in order: sum += exp(min - v_i);  potential = min - log1p(sum), DBL_MAX if that
+ *              is not below DBL_MAX.
+ *              fw(initial) = 0;  fw(t, q): over the trellis arcs into (t, q) in (p, arc position) order, v = extend(fw(t-1,
+ *              p), arcScore).   bw(T-1, q) = f64(final_weight(q)) if that is below +inf, else DBL_MAX;  bw(t, p), and
+ *              bw(initial): over the trellis arcs out of the node in arc order, v = extend(bw(t+1, q), arcScore).
+ *              out_log_total = bw(initial).  A node that reaches no final state keeps DBL_MAX.
+ *              An arc's log posterior: x = ((fw(source) + f64(arcScore)) + bw(target)) + (-bw(initial)), left to right in
+ *              f64; lp = f32(x) if x < FLT_MAX, else FLT_MAX.
+ *   4 items    per (column, mixture) that has a trellis arc: the lp of its arcs collected, in (source state, arc position)
+ *              order, the first initialising; clipped to [0, FLT_MAX].  Per column: min = FLT_MAX, lowered by every item
+ *              below it; w = lp - min; w = f32(exp(f64(-w))), 0 for an infinite w; sum = 0.0f + the w in ascending
+ *              mixture order; inv = 1.0f / sum, or 1 if the sum is 0; weight = w * inv.  An item is kept iff
+ *              weight > min_posterior; nothing is renormalised after that.
+ * Against the reference this fixes two orders that its std::sort leaves open (the order in which equal (time, emission)
+ * items are collected, and the one in which a frame's weights are summed) and evaluates the f32 steps' exp and log1p
+ * through f64; DESIGN.md section 17 bounds both.  tests/aligner_posterior_restatement.py restates this contract.
+ */
+
+/* The Baum-Welch call.  All pointers are DEVICE pointers; enqueued on `stream`, no synchronisation.  The FIRST posterior
+ * call on a handle allocates the posterior scratch, sized from the capacities given at creation (per cell two f64
+ * potentials and a mark; per frame 12 bytes, max_cells of them; min(n_mixtures, max_arcs) f32 for each of 1024 waves;
+ * the arcs as given and grouped by mixture), and uploads the batch's tables for this mode; later calls allocate nothing,
+ * and a later gmm_aligner_set_segments uploads them itself.  (set_segments builds them on the host with every batch.)
+ *   scores, n_table_frames, score_stride, pruning_threshold, stream     as for gmm_aligner_align_device
+ *   min_posterior      keep an item iff weight > min_posterior; 0 is the reference's filterWeightsGT(0.0)
+ *   max_items          the capacity of the three item arrays
+ *   out_item_frame, out_item_mixture [max_items] u32, out_item_weight [max_items] f64 (each holds a f32 value exactly):
+ *                      the compact list of the kept items, ordered by (table column, mixture) ascending; all three or
+ *                      none.  As they stand they are pair_frame, pair_mixture and pair_weight of
+ *                      gmm_estimator_accumulate_posteriors_device and its siblings
+ *   out_column_offset  [n_table_frames + 1] u32 or NULL: CSR into the list by table column; columns of no segment and of
+ *                      a segment without an alignment are empty
+ *   out_n_items        one u32 or NULL: the number of items the call produces.  Above max_items nothing past max_items is
+ *                      written, the list is invalid, the count is still exact
+ *   out_score          [n_segments] f32 or NULL: the Baum-Welch alignmentScore(), FLT_MAX without an alignment
+ *   out_hypotheses     [n_segments] u32 or NULL: as in the Viterbi call
+ *   out_log_total      [n_segments] f64 or NULL: bw(initial), DBL_MAX without an alignment
+ * Errors, each before anything is written: GMM_ERR_INVALID_ARGUMENT as for the align call, and for some but not all of
+ * the item arrays, or item arrays with max_items == 0; GMM_ERR_UNSUPPORTED for a segment of more than
+ * GMM_ALIGN_MAX_STATES_POSTERIOR states. */
+int gmm_aligner_posteriors_device(gmm_aligner* aligner, const float* scores, uint32_t n_table_frames,
+                                  uint32_t score_stride, float pruning_threshold, float min_posterior, uint32_t max_items,
+                                  uint32_t* out_item_frame, uint32_t* out_item_mixture, double* out_item_weight,
+                                  uint32_t* out_column_offset, uint32_t* out_n_items, float* out_score,
+                                  uint32_t* out_hypotheses, double* out_log_total, void* stream);
+
+/* The same call from a HOST table into HOST outputs; synchronous.  GMM_ERR_CAPACITY if the call produces more than
+ * max_items items: *out_n_items and the per-segment outputs are then still written, the item arrays and
+ * out_column_offset are not. */
+int gmm_aligner_posteriors_host(gmm_aligner* aligner, const float* scores, uint32_t n_table_frames, uint32_t score_stride,
+                                float pruning_threshold, float min_posterior, uint32_t max_items, uint32_t* out_item_frame,
+                                uint32_t* out_item_mixture, double* out_item_weight, uint32_t* out_column_offset,
+                                uint32_t* out_n_items, float* out_score, uint32_t* out_hypotheses, double* out_log_total);
 
 #ifdef __cplusplus
 }

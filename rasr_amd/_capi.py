@@ -26,6 +26,7 @@ GMM_MLLR_FULL = 1  # the kinds of MLLR statistics (a mask for gmm_mllr_create)
 GMM_MLLR_SHIFT = 2
 GMM_MLLR_NO_ID = 0xFFFFFFFF  # "none" in the tree arrays of gmm_mllr_estimate
 GMM_ALIGN_MAX_STATES = 6144  # include/rasr_gmm_align.h: the most states of one segment
+GMM_ALIGN_MAX_STATES_POSTERIOR = 2432  # the most states of one segment in a Baum-Welch (posteriors) call
 GMM_ALIGN_MAX_IN_ARCS = 65535  # the most arcs entering one state
 GMM_ALIGN_NONE = 0xFFFFFFFF  # the per-frame outputs of a segment without an alignment
 STATE_POSTERIOR_CHUNK = 256  # include/rasr_gmm.h GMM_STATE_POSTERIOR_CHUNK: part of the state posteriors' contract
@@ -369,6 +370,12 @@ PROTOTYPES = [
     ("gmm_aligner_align_host", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_void_p,
       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("gmm_aligner_posteriors_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_float,
+      ctypes.c_uint32] + [ctypes.c_void_p] * 9),
+    ("gmm_aligner_posteriors_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_float,
+      ctypes.c_uint32] + [ctypes.c_void_p] * 8),
     ("gmm_version", ctypes.c_char_p, []),
     ("gmm_kernel_id", ctypes.c_char_p, []),
 ]

@@ -19,6 +19,7 @@ from . import _capi
 from ._pairs import ptr as _ptr
 
 MAX_STATES = _capi.GMM_ALIGN_MAX_STATES
+MAX_STATES_POSTERIOR = _capi.GMM_ALIGN_MAX_STATES_POSTERIOR
 MAX_IN_ARCS = _capi.GMM_ALIGN_MAX_IN_ARCS
 NONE = _capi.GMM_ALIGN_NONE
 
@@ -170,6 +171,70 @@ class Aligner:
             ctypes.c_void_p(hyp.data_ptr()), ctypes.c_void_p(s) if s else None)
         _capi.check(rc, "gmm_aligner_align_device")
         return {"mixture": cols[0], "state": cols[1], "arc": cols[2], "score": score, "hypotheses": hyp}
+
+    def posteriors(self, scores, pruning_threshold: float = float("inf"), min_posterior: float = 0.0, max_items=None,
+                   n_table_frames=None, stream=None) -> dict:
+        """Baum-Welch alignment of the batch over `scores` (gmm_aligner_posteriors_*): the per-frame mixture posteriors
+        as a compact item list ordered by (table column, mixture).
+
+        Returns {"frame", "mixture"} (int32) and {"weight"} (float64, holding float32 values), trimmed to the number of
+        items -- as they stand pair_frame, pair_mixture and pair_weight of Estimator.accumulate_posteriors_device --,
+        "column_offset" [n_table_frames + 1] int32 (CSR into the list by table column), "n_items", "score" [n_segments]
+        float32 (FLT_MAX without an alignment), "hypotheses" [n_segments] int32 and "log_total" [n_segments] float64
+        (DBL_MAX without an alignment).  An item is kept iff its weight > min_posterior.
+        max_items is the capacity of the item arrays (default: n_table_frames * min(n_mixtures, 64)); a call that
+        produces more raises GmmError with code GMM_ERR_CAPACITY and the exact count in .n_items.
+        A torch CUDA tensor: the device call on `stream`; READING THE ITEM COUNT to trim the arrays IS ITS ONE
+        SYNCHRONISATION with the host.  A numpy array: the host call, synchronous, numpy outputs.  The first call on a
+        handle allocates the scratch of this mode."""
+        host = isinstance(scores, np.ndarray)
+        if host:
+            scores = np.ascontiguousarray(scores, dtype=np.float32)
+            if scores.ndim != 2 or scores.shape[0] != self.n_mixtures:
+                raise ValueError("scores must be [n_mixtures, >= n_table_frames]")
+        else:
+            import torch
+            if (scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1
+                    or scores.shape[0] != self.n_mixtures):
+                raise ValueError("scores must be a float32 [n_mixtures, >= n_table_frames] tensor with unit column stride")
+        f = int(scores.shape[1] if n_table_frames is None else n_table_frames)
+        cap = int(max(1, f * min(self.n_mixtures, 64)) if max_items is None else max_items)
+        if cap <= 0:
+            raise ValueError("max_items must be positive")
+        shapes = (("frame", cap, "int32"), ("mixture", cap, "int32"), ("weight", cap, "float64"),
+                  ("column_offset", f + 1, "int32"), ("n_items", 1, "int32"), ("score", self.n_segments, "float32"),
+                  ("hypotheses", self.n_segments, "int32"), ("log_total", self.n_segments, "float64"))
+        if host:
+            out = {k: np.zeros(n, dtype=t) for k, n, t in shapes}
+            rc = self._lib.gmm_aligner_posteriors_host(
+                self._h, _ptr(scores), f, scores.shape[1], float(pruning_threshold), float(min_posterior), cap,
+                *(_ptr(out[k]) for k, _, _ in shapes))
+            n = int(out["n_items"][0])
+            try:
+                _capi.check(rc, "gmm_aligner_posteriors_host")
+            except _capi.GmmError as err:
+                err.n_items = n  # exact when the code is GMM_ERR_CAPACITY
+                raise
+        else:
+            out = {k: torch.zeros(n, dtype=getattr(torch, t), device=scores.device) for k, n, t in shapes}
+            if stream is None:
+                stream = torch.cuda.current_stream(scores.device)
+            s = getattr(stream, "cuda_stream", stream)
+            rc = self._lib.gmm_aligner_posteriors_device(
+                self._h, ctypes.c_void_p(scores.data_ptr()), f, int(scores.stride(0)), float(pruning_threshold),
+                float(min_posterior), cap, *(ctypes.c_void_p(out[k].data_ptr()) for k, _, _ in shapes),
+                ctypes.c_void_p(s) if s else None)
+            _capi.check(rc, "gmm_aligner_posteriors_device")
+            n = int(out["n_items"].item())  # the one synchronisation
+            if n > cap:
+                err = _capi.GmmError(f"gmm_aligner_posteriors_device: the call produces {n} items, more than max_items "
+                                     f"{cap}")
+                err.code, err.n_items = _capi.GMM_ERR_CAPACITY, n
+                raise err
+        for k in ("frame", "mixture", "weight"):
+            out[k] = out[k][:n]
+        out["n_items"] = n
+        return out
 
     def _align_host(self, scores, pruning_threshold, n_table_frames, out_mixture, out_state, out_arc) -> dict:
         scores = np.ascontiguousarray(scores, dtype=np.float32)

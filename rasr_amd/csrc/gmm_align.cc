@@ -20,6 +20,20 @@ struct gmm_aligner {
     DeviceBuffer<float>        dInWeight, dFinalWeight;
     // the backpointers of one call
     DeviceBuffer<uint32_t> dCells;
+    // Baum-Welch mode.  `posterior` keeps the batch's tables for it on the host (AlignPlan's second half; the first is
+    // dropped): the first posterior call allocates everything below and uploads them, set_segments does after that
+    AlignPlan              posterior;
+    uint32_t               maxSegmentStates = 0;
+    bool                   posteriorReady = false;
+    DeviceBuffer<uint32_t> dArcOffset, dArcTarget, dArcMixture, dGroupOffset, dGroupMixture, dGroupArcOffset, dGroupSource,
+            dGroupTarget, dColSegment, dColFrameOffset;
+    DeviceBuffer<float>    dArcWeight, dGroupWeight;
+    // its scratch: per cell, per segment, per ordered frame, per item wave
+    DeviceBuffer<double>   dFwPot, dBwPot, dSegTotalInv;
+    DeviceBuffer<uint8_t>  dMark;
+    DeviceBuffer<uint32_t> dSegHas, dFrameCount;
+    DeviceBuffer<float>    dFrameMin, dFrameInv, dWaveWeights;
+    uint32_t               rowGroups = 0;
     // recorded by every align call on its stream; set_segments and destroy wait for it
     Event done;
     bool  pending = false;
@@ -106,6 +120,150 @@ int alignOn(gmm_aligner* h, const float* scores, uint32_t scoreStride, float pru
     return GMM_OK;
 }
 
+// the ordered frames of a batch fit 32 bits (the frame ranges are disjoint columns of a table)
+size_t maxFrames(const AlignCapacity& c) {
+    return static_cast<size_t>(c.maxCells < 0xffffffffull ? c.maxCells : 0xffffffffull);
+}
+
+// the batch's tables of the Baum-Welch mode, from the host copy
+int uploadPosterior(gmm_aligner* h) {
+    const AlignPlan& p = h->posterior;
+    GMM_HIP_CHECK(put(h->dArcOffset, p.arcOffset));
+    GMM_HIP_CHECK(put(h->dArcTarget, p.arcTarget));
+    GMM_HIP_CHECK(put(h->dArcMixture, p.arcMixture));
+    GMM_HIP_CHECK(put(h->dArcWeight, p.arcWeight));
+    GMM_HIP_CHECK(put(h->dGroupOffset, p.groupOffset));
+    GMM_HIP_CHECK(put(h->dGroupMixture, p.groupMixture));
+    GMM_HIP_CHECK(put(h->dGroupArcOffset, p.groupArcOffset));
+    GMM_HIP_CHECK(put(h->dGroupSource, p.groupSource));
+    GMM_HIP_CHECK(put(h->dGroupTarget, p.groupTarget));
+    GMM_HIP_CHECK(put(h->dGroupWeight, p.groupWeight));
+    GMM_HIP_CHECK(put(h->dColSegment, p.colSegment));
+    const std::vector<uint32_t> frameOffset(p.colFrameOffset.begin(), p.colFrameOffset.end());
+    GMM_HIP_CHECK(put(h->dColFrameOffset, frameOffset));
+    GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
+    return GMM_OK;
+}
+
+// the first posterior call: the mode's tables and scratch, sized from the capacities
+int preparePosterior(gmm_aligner* h) {
+    if (h->posteriorReady)
+        return GMM_OK;
+    const AlignCapacity& c = h->cap;
+    const size_t         frames = maxFrames(c);
+    GMM_HIP_CHECK(h->dArcOffset.alloc(static_cast<size_t>(c.maxStates) + 1));
+    GMM_HIP_CHECK(h->dArcTarget.alloc(c.maxArcs));
+    GMM_HIP_CHECK(h->dArcMixture.alloc(c.maxArcs));
+    GMM_HIP_CHECK(h->dArcWeight.alloc(c.maxArcs));
+    GMM_HIP_CHECK(h->dGroupOffset.alloc(static_cast<size_t>(c.maxSegments) + 1));
+    GMM_HIP_CHECK(h->dGroupMixture.alloc(c.maxArcs));
+    GMM_HIP_CHECK(h->dGroupArcOffset.alloc(static_cast<size_t>(c.maxArcs) + 1));
+    GMM_HIP_CHECK(h->dGroupSource.alloc(c.maxArcs));
+    GMM_HIP_CHECK(h->dGroupTarget.alloc(c.maxArcs));
+    GMM_HIP_CHECK(h->dGroupWeight.alloc(c.maxArcs));
+    GMM_HIP_CHECK(h->dColSegment.alloc(c.maxSegments));
+    GMM_HIP_CHECK(h->dColFrameOffset.alloc(static_cast<size_t>(c.maxSegments) + 1));
+    GMM_HIP_CHECK(h->dFwPot.alloc(c.maxCells));
+    GMM_HIP_CHECK(h->dBwPot.alloc(c.maxCells));
+    GMM_HIP_CHECK(h->dMark.alloc(c.maxCells));
+    GMM_HIP_CHECK(h->dSegTotalInv.alloc(c.maxSegments));
+    GMM_HIP_CHECK(h->dSegHas.alloc(c.maxSegments));
+    GMM_HIP_CHECK(h->dFrameCount.alloc(frames + 1));
+    GMM_HIP_CHECK(h->dFrameMin.alloc(frames));
+    GMM_HIP_CHECK(h->dFrameInv.alloc(frames));
+    h->rowGroups = c.nMixtures < c.maxArcs ? c.nMixtures : c.maxArcs;
+    GMM_HIP_CHECK(h->dWaveWeights.alloc(static_cast<size_t>(kAlignItemWaves) * h->rowGroups));
+    const int rc = uploadPosterior(h);
+    if (rc != GMM_OK)
+        return rc;
+    h->posteriorReady = true;
+    return GMM_OK;
+}
+
+// the checks of both posterior calls; nothing is written or enqueued before they pass
+int checkPosteriorCall(const gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
+                       uint32_t maxItems, const void* itemFrame, const void* itemMixture, const void* itemWeight,
+                       const void* columnOffset, const void* nItems, const void* outScore, const void* outHypotheses,
+                       const void* logTotal) {
+    const bool items = itemFrame || itemMixture || itemWeight;
+    const int  rc = checkAlignCall(h, scores, nTableFrames, scoreStride, itemFrame, columnOffset, nItems,
+                                   outScore ? outScore : logTotal, outHypotheses);
+    if (rc != GMM_OK)
+        return rc;
+    if (items && !(itemFrame && itemMixture && itemWeight))
+        return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: out_item_frame, out_item_mixture and out_item_weight go together");
+    if (items && maxItems == 0)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: item arrays with max_items 0");
+    if (h->maxSegmentStates > GMM_ALIGN_MAX_STATES_POSTERIOR)
+        return fail(GMM_ERR_UNSUPPORTED, "aligner: a segment has " + std::to_string(h->maxSegmentStates) +
+                                                 " states, more than GMM_ALIGN_MAX_STATES_POSTERIOR " +
+                                                 std::to_string(GMM_ALIGN_MAX_STATES_POSTERIOR));
+    if (h->posterior.nFrames > 0xffffffffull)
+        return fail(GMM_ERR_UNSUPPORTED, "aligner: 2^32 frames or more in one batch");
+    return GMM_OK;
+}
+
+int posteriorsOn(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride, float pruning,
+                 float minPosterior, uint32_t maxItems, uint32_t* itemFrame, uint32_t* itemMixture, double* itemWeight,
+                 uint32_t* columnOffset, uint32_t* nItems, float* outScore, uint32_t* outHypotheses, double* logTotal,
+                 hipStream_t stream) {
+    const int rc = preparePosterior(h);
+    if (rc != GMM_OK)
+        return rc;
+    AlignPosteriorArgs a{};
+    a.segments        = h->dSegments.get();
+    a.order           = h->dOrder.get();
+    a.inOffset        = h->dInOffset.get();
+    a.inSource        = h->dInSource.get();
+    a.inMixture       = h->dInMixture.get();
+    a.inWeight        = h->dInWeight.get();
+    a.finalWeight     = h->dFinalWeight.get();
+    a.arcOffset       = h->dArcOffset.get();
+    a.arcTarget       = h->dArcTarget.get();
+    a.arcMixture      = h->dArcMixture.get();
+    a.arcWeight       = h->dArcWeight.get();
+    a.groupOffset     = h->dGroupOffset.get();
+    a.groupMixture    = h->dGroupMixture.get();
+    a.groupArcOffset  = h->dGroupArcOffset.get();
+    a.groupSource     = h->dGroupSource.get();
+    a.groupTarget     = h->dGroupTarget.get();
+    a.groupWeight     = h->dGroupWeight.get();
+    a.colSegment      = h->dColSegment.get();
+    a.colFrameOffset  = h->dColFrameOffset.get();
+    a.scores          = scores;
+    a.scoreStride     = scoreStride;
+    a.nTableFrames    = nTableFrames;
+    a.pruning         = pruning;
+    a.minPosterior    = minPosterior;
+    a.maxItems        = maxItems;
+    a.fwPot           = h->dFwPot.get();
+    a.bwPot           = h->dBwPot.get();
+    a.mark            = h->dMark.get();
+    a.segTotalInv     = h->dSegTotalInv.get();
+    a.segHas          = h->dSegHas.get();
+    a.frameMin        = h->dFrameMin.get();
+    a.frameInv        = h->dFrameInv.get();
+    a.frameCount      = h->dFrameCount.get();
+    a.waveWeights     = h->dWaveWeights.get();
+    a.rowGroups       = h->rowGroups;
+    a.outItemFrame    = itemFrame;
+    a.outItemMixture  = itemMixture;
+    a.outItemWeight   = itemWeight;
+    a.outColumnOffset = columnOffset;
+    a.outNItems       = nItems;
+    a.outScore        = outScore;
+    a.outHypotheses   = outHypotheses;
+    a.outLogTotal     = logTotal;
+    a.nSegments       = h->nSegments;
+    a.rowStates       = h->rowStates;
+    a.nFrames         = static_cast<uint32_t>(h->posterior.nFrames);
+    const hipError_t e = launchAlignPosteriors(a, stream);
+    GMM_HIP_CHECK(hipEventRecord(h->done.get(), stream));
+    h->pending = true;
+    GMM_HIP_CHECK(e);
+    return GMM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -161,9 +319,20 @@ int gmm_aligner_set_segments(gmm_aligner* h, const gmm_align_graphs* graphs) {
     GMM_HIP_CHECK(put(h->dInWeight, plan.inWeight));
     GMM_HIP_CHECK(put(h->dFinalWeight, plan.finalWeight));
     GMM_HIP_CHECK(hipStreamSynchronize(nullptr));  // done before a call on any other stream
-    h->rowStates = (plan.maxSegmentStates + 63u) & ~63u;
-    h->frameEnd  = plan.frameEnd;
-    h->nSegments = static_cast<uint32_t>(plan.segments.size());
+    const uint32_t nSegments = static_cast<uint32_t>(plan.segments.size());
+    // the Baum-Welch mode's tables stay on the host until a posterior call has made room for them on the device
+    for (std::vector<uint32_t>* v : {&plan.order, &plan.inOffset, &plan.inSource, &plan.inArc, &plan.inMixture})
+        std::vector<uint32_t>().swap(*v);
+    std::vector<float>().swap(plan.inWeight);
+    std::vector<float>().swap(plan.finalWeight);
+    std::vector<AlignSegment>().swap(plan.segments);
+    h->posterior = std::move(plan);
+    if (h->posteriorReady && (rc = uploadPosterior(h)) != GMM_OK)
+        return rc;
+    h->maxSegmentStates = h->posterior.maxSegmentStates;
+    h->rowStates        = (h->posterior.maxSegmentStates + 63u) & ~63u;
+    h->frameEnd         = h->posterior.frameEnd;
+    h->nSegments        = nSegments;
     return GMM_OK;
 }
 
@@ -219,6 +388,80 @@ int gmm_aligner_align_host(gmm_aligner* h, const float* scores, uint32_t nTableF
         GMM_HIP_CHECK(hipMemcpy(outScore, dScore.get(), S * sizeof(float), hipMemcpyDeviceToHost));
     if (outHypotheses)
         GMM_HIP_CHECK(hipMemcpy(outHypotheses, dHypotheses.get(), S * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
+    return GMM_OK;
+}
+
+int gmm_aligner_posteriors_device(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
+                                  float pruning, float minPosterior, uint32_t maxItems, uint32_t* itemFrame,
+                                  uint32_t* itemMixture, double* itemWeight, uint32_t* columnOffset, uint32_t* nItems,
+                                  float* outScore, uint32_t* outHypotheses, double* logTotal, void* stream) {
+    const int rc = checkPosteriorCall(h, scores, nTableFrames, scoreStride, maxItems, itemFrame, itemMixture, itemWeight,
+                                      columnOffset, nItems, outScore, outHypotheses, logTotal);
+    if (rc != GMM_OK)
+        return rc;
+    GMM_HIP_CHECK(hipSetDevice(h->device));
+    return posteriorsOn(h, scores, nTableFrames, scoreStride, pruning, minPosterior, maxItems, itemFrame, itemMixture,
+                        itemWeight, columnOffset, nItems, outScore, outHypotheses, logTotal,
+                        static_cast<hipStream_t>(stream));
+}
+
+int gmm_aligner_posteriors_host(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
+                                float pruning, float minPosterior, uint32_t maxItems, uint32_t* itemFrame,
+                                uint32_t* itemMixture, double* itemWeight, uint32_t* columnOffset, uint32_t* nItems,
+                                float* outScore, uint32_t* outHypotheses, double* logTotal) {
+    int rc = checkPosteriorCall(h, scores, nTableFrames, scoreStride, maxItems, itemFrame, itemMixture, itemWeight,
+                                columnOffset, nItems, outScore, outHypotheses, logTotal);
+    if (rc != GMM_OK)
+        return rc;
+    GMM_HIP_CHECK(hipSetDevice(h->device));
+    if ((rc = waitDone(h)) != GMM_OK)
+        return rc;
+    const size_t           F = nTableFrames, M = h->cap.nMixtures, S = h->nSegments, I = itemFrame ? maxItems : 0;
+    DeviceBuffer<float>    dTable, dScore;
+    DeviceBuffer<uint32_t> dItems, dColumnOffset, dCount, dHypotheses;  // dItems: frame, mixture
+    DeviceBuffer<double>   dWeight, dLogTotal;
+    GMM_HIP_CHECK(dTable.alloc(M * F));
+    GMM_HIP_CHECK(dItems.alloc(2 * I));
+    GMM_HIP_CHECK(dWeight.alloc(I));
+    GMM_HIP_CHECK(dColumnOffset.alloc(F + 1));
+    GMM_HIP_CHECK(dCount.alloc(1));
+    GMM_HIP_CHECK(dScore.alloc(S));
+    GMM_HIP_CHECK(dHypotheses.alloc(S));
+    GMM_HIP_CHECK(dLogTotal.alloc(S));
+    if (F)
+        GMM_HIP_CHECK(hipMemcpy2D(dTable.get(), F * sizeof(float), scores, static_cast<size_t>(scoreStride) * sizeof(float),
+                                  F * sizeof(float), M, hipMemcpyHostToDevice));
+    rc = posteriorsOn(h, dTable.get(), nTableFrames, nTableFrames, pruning, minPosterior, maxItems,
+                      I ? dItems.get() : nullptr, I ? dItems.get() + I : nullptr, I ? dWeight.get() : nullptr,
+                      columnOffset ? dColumnOffset.get() : nullptr, dCount.get(), outScore ? dScore.get() : nullptr,
+                      outHypotheses ? dHypotheses.get() : nullptr, logTotal ? dLogTotal.get() : nullptr, nullptr);
+    if (rc != GMM_OK) {
+        (void)hipStreamSynchronize(nullptr);  // the buffers go with this scope
+        return rc;
+    }
+    uint32_t count = 0;
+    GMM_HIP_CHECK(hipMemcpy(&count, dCount.get(), sizeof(count), hipMemcpyDeviceToHost));
+    if (nItems)
+        *nItems = count;
+    if (outScore)
+        GMM_HIP_CHECK(hipMemcpy(outScore, dScore.get(), S * sizeof(float), hipMemcpyDeviceToHost));
+    if (outHypotheses)
+        GMM_HIP_CHECK(hipMemcpy(outHypotheses, dHypotheses.get(), S * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (logTotal)
+        GMM_HIP_CHECK(hipMemcpy(logTotal, dLogTotal.get(), S * sizeof(double), hipMemcpyDeviceToHost));
+    if (I && count > maxItems) {
+        GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
+        return fail(GMM_ERR_CAPACITY, "aligner: the call produces " + std::to_string(count) + " items, more than max_items " +
+                                              std::to_string(maxItems));
+    }
+    if (I && count) {
+        GMM_HIP_CHECK(hipMemcpy(itemFrame, dItems.get(), count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        GMM_HIP_CHECK(hipMemcpy(itemMixture, dItems.get() + I, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        GMM_HIP_CHECK(hipMemcpy(itemWeight, dWeight.get(), count * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (columnOffset)
+        GMM_HIP_CHECK(hipMemcpy(columnOffset, dColumnOffset.get(), (F + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
     return GMM_OK;
 }

@@ -40,4 +40,52 @@ struct AlignArgs {
 
 hipError_t launchAlign(const AlignArgs& a, hipStream_t stream);
 
+// The Baum-Welch call (gmm_kernels_align_posterior.hip).  LDS of a segment's workgroup: two f64 potential rows, two f32
+// score rows and two rows of active marks (GMM_ALIGN_MAX_STATES_POSTERIOR); the rows are rounded up to 64 states
+constexpr uint32_t kAlignPosteriorLdsBytesPerState = 2 * (sizeof(double) + sizeof(float) + 1);
+static_assert(((GMM_ALIGN_MAX_STATES_POSTERIOR + 63u) & ~63u) * kAlignPosteriorLdsBytesPerState <= 63 * 1024,
+              "the rows of the largest segment fit in LDS beside the reductions");
+static_assert(GMM_ALIGN_MAX_STATES_POSTERIOR <= GMM_ALIGN_MAX_STATES, "set_segments accepts what the posterior call does");
+// the item passes run one wave per frame, kAlignItemWaves of them at most; each has a row of the weight scratch
+constexpr uint32_t kAlignItemWaves = 1024;
+
+struct AlignPosteriorArgs {
+    // the batch
+    const AlignSegment* segments;
+    const uint32_t*     order;
+    const uint32_t *    inOffset, *inSource, *inMixture;
+    const float *       inWeight, *finalWeight;
+    const uint32_t *    arcOffset, *arcTarget, *arcMixture;  // the arcs as given: CSR by global source state
+    const float*        arcWeight;
+    const uint32_t *    groupOffset, *groupMixture, *groupArcOffset, *groupSource, *groupTarget;
+    const float*        groupWeight;
+    const uint32_t *    colSegment, *colFrameOffset;  // the segments by table column, their ordered frames
+    // the call
+    const float* scores;
+    uint32_t     scoreStride, nTableFrames;
+    float        pruning, minPosterior;
+    uint32_t     maxItems;
+    // the scratch: per (frame, state) cell the forward and backward potentials and the active mark; per segment
+    // -bw[initial] and whether it has an alignment; per ordered frame the minimum, the inverse sum and the item count
+    // (then offset); per item wave a row of rowGroups weights
+    double * fwPot, *bwPot;
+    uint8_t* mark;
+    double*  segTotalInv;
+    uint32_t* segHas;
+    float *   frameMin, *frameInv;
+    uint32_t* frameCount;  // [nFrames + 1]
+    float*    waveWeights;
+    uint32_t  rowGroups;
+    // the outputs
+    uint32_t *outItemFrame, *outItemMixture;
+    double*   outItemWeight;
+    uint32_t *outColumnOffset, *outNItems;
+    float*    outScore;
+    uint32_t* outHypotheses;
+    double*   outLogTotal;
+    uint32_t  nSegments, rowStates, nFrames;
+};
+
+hipError_t launchAlignPosteriors(const AlignPosteriorArgs& a, hipStream_t stream);
+
 }  // namespace rasr_gmm

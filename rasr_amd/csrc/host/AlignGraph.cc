@@ -139,6 +139,55 @@ int buildAlignPlan(const gmm_align_graphs& g, const AlignCapacity& cap, AlignPla
             }
     }
     p.finalWeight.assign(g.final_weight, g.final_weight + nStates);
+    // the Baum-Welch call: the arcs as given ...
+    p.arcOffset.assign(g.arc_offset, g.arc_offset + nStates + 1);
+    if (nArcs) {
+        p.arcTarget.assign(g.arc_target, g.arc_target + nArcs);
+        p.arcMixture.assign(g.arc_mixture, g.arc_mixture + nArcs);
+        p.arcWeight.assign(g.arc_weight, g.arc_weight + nArcs);
+    }
+    // ... each segment's arcs grouped by mixture: a stable sort of the arcs, which stand in (source state, arc
+    // position) order, keeps that order inside a group ...
+    p.groupOffset.assign(1, 0u);
+    p.groupArcOffset.assign(1, 0u);
+    p.groupSource.reserve(nArcs);
+    p.groupTarget.reserve(nArcs);
+    p.groupWeight.reserve(nArcs);
+    std::vector<uint32_t> source, byMixture;
+    for (uint32_t s = 0; s < S; ++s) {
+        const AlignSegment& d  = p.segments[s];
+        const uint32_t      a0 = g.arc_offset[d.stateBegin], a1 = g.arc_offset[d.stateBegin + d.nStates];
+        source.resize(a1 - a0);
+        for (uint32_t src = 0; src < d.nStates; ++src)
+            for (uint32_t a = g.arc_offset[d.stateBegin + src]; a < g.arc_offset[d.stateBegin + src + 1]; ++a)
+                source[a - a0] = src;
+        byMixture.resize(a1 - a0);
+        std::iota(byMixture.begin(), byMixture.end(), a0);
+        std::stable_sort(byMixture.begin(), byMixture.end(),
+                         [&](uint32_t a, uint32_t b) { return g.arc_mixture[a] < g.arc_mixture[b]; });
+        for (size_t i = 0; i < byMixture.size(); ++i) {
+            const uint32_t a = byMixture[i];
+            if (i == 0 || g.arc_mixture[a] != g.arc_mixture[byMixture[i - 1]]) {
+                if (i)
+                    p.groupArcOffset.push_back(static_cast<uint32_t>(p.groupSource.size()));
+                p.groupMixture.push_back(g.arc_mixture[a]);
+            }
+            p.groupSource.push_back(source[a - a0]);
+            p.groupTarget.push_back(g.arc_target[a]);
+            p.groupWeight.push_back(g.arc_weight[a]);
+        }
+        if (!byMixture.empty())
+            p.groupArcOffset.push_back(static_cast<uint32_t>(p.groupSource.size()));
+        const uint32_t groups = static_cast<uint32_t>(p.groupMixture.size()) - p.groupOffset.back();
+        p.maxSegmentGroups    = std::max(p.maxSegmentGroups, groups);
+        p.groupOffset.push_back(static_cast<uint32_t>(p.groupMixture.size()));
+    }
+    // ... and the segments by table column
+    p.colSegment = byBegin;
+    p.colFrameOffset.assign(1, 0);
+    for (uint32_t i = 0; i < S; ++i)
+        p.colFrameOffset.push_back(p.colFrameOffset.back() + p.segments[byBegin[i]].nFrames);
+    p.nFrames = p.colFrameOffset.back();
     // the longest segments first: a workgroup's time grows with its frames and with the arcs it scans per frame
     p.order.resize(S);
     std::iota(p.order.begin(), p.order.end(), 0u);

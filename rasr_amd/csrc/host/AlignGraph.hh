@@ -1,6 +1,8 @@
 // AlignGraph.hh -- a batch of alignment automata (gmm_align_graphs) validated and turned into what the alignment kernel
 // reads: the segment descriptors and the incoming-arc lists per target state, ordered by (source state, arc position).
-// Plain C++, no HIP (tests/cpp/align_graph_test.cc runs it alone).
+// For the Baum-Welch call it also keeps the arcs as given (the backward pass walks a state's outgoing arcs), groups each
+// segment's arcs by mixture and lists the segments by table column.
+// Plain C++, no HIP (tests/cpp/align_graph_test.cc and tests/cpp/align_posterior_graph_test.cc run it alone).
 #pragma once
 
 #include <cstdint>
@@ -41,6 +43,21 @@ struct AlignPlan {
     uint32_t                  maxSegmentStates = 0;  // the largest segment
     uint64_t                  frameEnd = 0;          // the largest frame_begin + n_frames
     uint64_t                  nCells = 0;
+    // The Baum-Welch call (gmm_aligner_posteriors_*), built with every plan:
+    // the arcs as given, CSR by global source state
+    std::vector<uint32_t> arcOffset, arcTarget, arcMixture;
+    std::vector<float>    arcWeight;
+    // the arcs of every segment grouped by mixture: segment s owns the groups groupOffset[s] .. [s+1], in ascending
+    // mixture order; group g is the mixture groupMixture[g] and owns the entries groupArcOffset[g] .. [g+1] of
+    // groupSource / groupTarget / groupWeight, which keep the (source state, arc position) order
+    std::vector<uint32_t> groupOffset, groupMixture, groupArcOffset, groupSource, groupTarget;
+    std::vector<float>    groupWeight;
+    uint32_t              maxSegmentGroups = 0;
+    // the segments by ascending frame_begin: colSegment[i] is the i-th, its frames are the ordered frames
+    // colFrameOffset[i] .. [i+1] (the order of the item list); nFrames in all
+    std::vector<uint32_t> colSegment;
+    std::vector<uint64_t> colFrameOffset;
+    uint64_t              nFrames = 0;
 };
 
 // GMM_OK, or the status gmm_aligner_set_segments documents with *message set; out is complete or untouched.
