@@ -13,9 +13,9 @@
  *   Aligner::feed(Scorer)                                         src/Search/Aligner.cc:585-592
  *   Aligner::SearchSpace::finalStatePotential                     src/Search/Aligner.cc:376-396
  *   Aligner::SearchSpace::getAlignmentFsaViterbi                  src/Search/Aligner.cc:398-436
- * Baum-Welch mode (the per-frame mixture posteriors) is gmm_aligner_posteriors_*, described further down.
- * Not covered: n-best pruning, the threshold-increase loop of
- * feed(vector) -- out_score and out_hypotheses are what a caller needs to run it --, per-frame local scores, building
+ * Baum-Welch mode (the per-frame mixture posteriors) is gmm_aligner_posteriors_*, described further down; the
+ * threshold-increase loop of feed(vector) and n-best pruning are the gmm_aligner_*_search_* calls at the end.
+ * Not covered: per-frame local scores, building
  * the automata from a lexicon or from allophone states, word lattices, a RASR-side adapter.
  *
  * THE MODEL.  A segment has an automaton: states, arcs (target, emission label = a mixture index, f32 weight), an
@@ -149,8 +149,8 @@ int gmm_aligner_align_host(gmm_aligner* aligner, const float* scores, uint32_t n
  *   Fsa::posterior64                                                                src/Fsa/Sssp.cc:67-222
  *   LogSemiring::collect                                                            src/Fsa/tRealSemiring.cc:130-146
  *   Alignment::combineItems .. filterWeightsGT                                      src/Speech/Alignment.cc:442-578
- * Not covered: use-partial-sums, a positive min-weight (the arc-level prunePosterior), n-best pruning, the
- * threshold-increase loop of feed(vector), gamma scaling, the state-posteriors statistics channel, a RASR-side adapter.
+ * Not covered: use-partial-sums, a positive min-weight (the arc-level prunePosterior), gamma scaling, the
+ * state-posteriors statistics channel, a RASR-side adapter.
  *
  * THE NUMERIC CONTRACT of this mode.  Every f32 or f64 add, subtract, multiply and divide is one correctly rounded
  * operation, nothing is contracted; every exp and log1p is evaluated in f64 on the exactly widened argument and, in an
@@ -224,6 +224,88 @@ int gmm_aligner_posteriors_host(gmm_aligner* aligner, const float* scores, uint3
                                 float pruning_threshold, float min_posterior, uint32_t max_items, uint32_t* out_item_frame,
                                 uint32_t* out_item_mixture, double* out_item_weight, uint32_t* out_column_offset,
                                 uint32_t* out_n_items, float* out_score, uint32_t* out_hypotheses, double* out_log_total);
+
+/*
+ * THE SEARCH: the pruning-threshold search of Search::Aligner::feed(vector) and the n-best pruning of prune, in both
+ * modes, inside the one call:
+ *   Aligner::feed(const std::vector<Scorer>&)                     src/Search/Aligner.cc:594-621
+ *   Aligner::SearchSpace::prune (n-best)                          src/Search/Aligner.cc:254-276
+ *   Core::isAlmostEqual(f32, f32)                                 src/Core/Utility.hh:316-321
+ * THE NUMERIC CONTRACT: f32, every operation one rounding, the result the same bit for bit for every batch composition,
+ * launch geometry and run (the only atomics are integer counts).  Per segment, independently of the others:
+ *   schedule   t = min_pruning; the next t = t * increment_factor, one f32 multiply.  A pass runs while t <= max_pruning.
+ *   a pass     the fixed-threshold contract above from `start` to `end` (in Baum-Welch mode: step 1, the f32 search) with
+ *              pruning_threshold = t and the n-best step below in `prune`.  It gives score (the value of out_score) and
+ *              hypotheses, counted from 0 in every pass.
+ *   after it   1  if increment_factor <= 1: stop.
+ *              2  ok = (score != FLT_MAX) && ((double)hypotheses / (double)n_frames >= min_average_hypotheses)
+ *              3  if ok and !until_no_score_difference: stop.
+ *              4  if ok, this is not the first pass, and almost_equal(score, previous): stop.
+ *              5  otherwise previous = score (it starts as FLT_MAX) and the next threshold follows.
+ *              almost_equal(a, b) = fabsf(a - b) < ((fabsf(a) + fabsf(b)) + FLT_MIN) * FLT_EPSILON, left to right.
+ *   outputs    those of the last pass run, also when the schedule is exhausted: a segment that never reached a final
+ *              state then has GMM_ALIGN_NONE columns, FLT_MAX and no items.  out_threshold is that pass's t,
+ *              out_iterations the number of passes.  In Baum-Welch mode steps 2 to 4 are those of the last pass.
+ *   n-best     in `prune`, with R the number of reached states of the frame.  min and threshold = min + t are formed
+ *              first, over all reached states.  If n_best < R: with the reached states ordered by (score ascending,
+ *              state index ascending; -0 equals +0), every state behind the first n_best gets score = threshold + 1.0f
+ *              (one f32 add), which stays its score if it survives.  Then, as before, a state is active iff
+ *              score <= threshold: the demoted states go while threshold + 1 > threshold in f32 (always below 2^24);
+ *              where the sum rounds back to threshold (always from 2^25 on, and between 2^24 and 2^25 for every second
+ *              value, a tie rounding to even) they stay with the new score, as in the reference.  The reference's std::nth_element leaves open which of
+ *              several equal scores at the cut survive; the state order closes that, and the result is the reference's
+ *              wherever the n_best-th and the next score differ.  With NaN scores the step is unspecified; the call
+ *              stays in bounds and terminates.
+ * tests/aligner_search_restatement.py restates this contract.
+ */
+
+/* The most thresholds a schedule may have.  From FLT_MIN to FLT_MAX with a factor of 2 there are 254, so no configuration
+ * with a factor of 2 or more is refused; a finite max_pruning and this cap bound the running time of every kernel (a
+ * factor of 1 + 2^-23 would otherwise run up to 2^31 passes). */
+#define GMM_ALIGN_MAX_ITERATIONS 256
+
+typedef struct gmm_align_search {
+    float    min_pruning;               /* min-acoustic-pruning,  default 50           */
+    float    max_pruning;               /* max-acoustic-pruning,  default FLT_MAX      */
+    float    increment_factor;          /* acoustic-pruning-increment-factor, default 2 */
+    double   min_average_hypotheses;    /* min-average-number-of-states, default 0     */
+    int      until_no_score_difference; /* increase-pruning-until-no-score-difference, default 1 */
+    uint32_t n_best;                    /* n-best-pruning, default 0x7fffffff          */
+} gmm_align_search;
+
+/* The reference's defaults, as listed. */
+void gmm_default_align_search(gmm_align_search* search);
+
+/* gmm_aligner_align_device / _host with the search in place of pruning_threshold, and two more per-segment outputs,
+ * either of which may be NULL (they do not count as "an output requested"):
+ *   out_threshold   [n_segments] f32: the threshold of the last pass
+ *   out_iterations  [n_segments] u32: the number of passes
+ * The device call still synchronizes nothing and allocates nothing.  Beyond the errors of the sibling call,
+ * GMM_ERR_INVALID_ARGUMENT before anything is written for: a NULL search; a NaN in any field; min_pruning < FLT_MIN;
+ * max_pruning not finite; min_pruning > max_pruning; increment_factor <= 1 with min_pruning != max_pruning (the
+ * reference's criticalError); n_best == 0; a schedule of more than GMM_ALIGN_MAX_ITERATIONS thresholds. */
+int gmm_aligner_align_search_device(gmm_aligner* aligner, const float* scores, uint32_t n_table_frames,
+                                    uint32_t score_stride, const gmm_align_search* search, uint32_t* out_mixture,
+                                    uint32_t* out_state, uint32_t* out_arc, float* out_score, uint32_t* out_hypotheses,
+                                    float* out_threshold, uint32_t* out_iterations, void* stream);
+int gmm_aligner_align_search_host(gmm_aligner* aligner, const float* scores, uint32_t n_table_frames,
+                                  uint32_t score_stride, const gmm_align_search* search, uint32_t* out_mixture,
+                                  uint32_t* out_state, uint32_t* out_arc, float* out_score, uint32_t* out_hypotheses,
+                                  float* out_threshold, uint32_t* out_iterations);
+
+/* gmm_aligner_posteriors_device / _host likewise; the first-use allocation of the Baum-Welch mode is the same one. */
+int gmm_aligner_posteriors_search_device(gmm_aligner* aligner, const float* scores, uint32_t n_table_frames,
+                                         uint32_t score_stride, const gmm_align_search* search, float min_posterior,
+                                         uint32_t max_items, uint32_t* out_item_frame, uint32_t* out_item_mixture,
+                                         double* out_item_weight, uint32_t* out_column_offset, uint32_t* out_n_items,
+                                         float* out_score, uint32_t* out_hypotheses, double* out_log_total,
+                                         float* out_threshold, uint32_t* out_iterations, void* stream);
+int gmm_aligner_posteriors_search_host(gmm_aligner* aligner, const float* scores, uint32_t n_table_frames,
+                                       uint32_t score_stride, const gmm_align_search* search, float min_posterior,
+                                       uint32_t max_items, uint32_t* out_item_frame, uint32_t* out_item_mixture,
+                                       double* out_item_weight, uint32_t* out_column_offset, uint32_t* out_n_items,
+                                       float* out_score, uint32_t* out_hypotheses, double* out_log_total,
+                                       float* out_threshold, uint32_t* out_iterations);
 
 #ifdef __cplusplus
 }

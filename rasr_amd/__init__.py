@@ -7,7 +7,7 @@ gfx950 + host-side model preparation); this package only binds it.
 from ._capi import (BATCH_DIAGONAL_MAXIMUM_FAST, BATCH_DIAGONAL_MAXIMUM_FLOAT, BATCH_DIAGONAL_MAXIMUM_INT,
                     DEFAULT_WEIGHT_THRESHOLD, DIAGONAL_MAXIMUM, LIB_PATH, SCORER_TYPES, SIMD_DIAGONAL_MAXIMUM, STATE_POSTERIOR_CHUNK,
                     GmmError, load_library)
-from .aligner import Aligner, batch_graphs, linear_hmm_graph
+from .aligner import Aligner, AlignSearch, batch_graphs, linear_hmm_graph
 from .adaptation import AffineTransformAccumulator, estimate_affine_transform
 from .estimator import (Estimator, combine_discriminative_estimators, combine_estimators, ebw_config,
                         ebw_iteration_constants, estimate_ebw)
@@ -26,5 +26,5 @@ __all__ = [
     "ebw_config", "DEFAULT_WEIGHT_THRESHOLD", "STATE_POSTERIOR_CHUNK", "float_spread_bound",
     "AffineTransformAccumulator", "estimate_affine_transform",
     "MLLR_KINDS", "MllrAccumulator", "estimate_mllr", "adapt_means",
-    "Aligner", "batch_graphs", "linear_hmm_graph",
+    "Aligner", "AlignSearch", "batch_graphs", "linear_hmm_graph",
 ]

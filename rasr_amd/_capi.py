@@ -29,6 +29,7 @@ GMM_ALIGN_MAX_STATES = 6144  # include/rasr_gmm_align.h: the most states of one 
 GMM_ALIGN_MAX_STATES_POSTERIOR = 2432  # the most states of one segment in a Baum-Welch (posteriors) call
 GMM_ALIGN_MAX_IN_ARCS = 65535  # the most arcs entering one state
 GMM_ALIGN_NONE = 0xFFFFFFFF  # the per-frame outputs of a segment without an alignment
+GMM_ALIGN_MAX_ITERATIONS = 256  # the most thresholds of a search schedule
 STATE_POSTERIOR_CHUNK = 256  # include/rasr_gmm.h GMM_STATE_POSTERIOR_CHUNK: part of the state posteriors' contract
 # GMM_ESTIMATOR_DEFAULT_WEIGHT_THRESHOLD: Core::Type<f32>::epsilon, the Baum-Welch weightThreshold_
 DEFAULT_WEIGHT_THRESHOLD = 2.0 ** -23
@@ -142,6 +143,17 @@ class AlignGraphs(ctypes.Structure):  # gmm_align_graphs
         ("final_weight", ctypes.c_void_p),
         ("frame_begin", ctypes.c_void_p),
         ("n_frames", ctypes.c_void_p),
+    ]
+
+
+class AlignSearchStruct(ctypes.Structure):  # gmm_align_search
+    _fields_ = [
+        ("min_pruning", ctypes.c_float),
+        ("max_pruning", ctypes.c_float),
+        ("increment_factor", ctypes.c_float),
+        ("min_average_hypotheses", ctypes.c_double),
+        ("until_no_score_difference", ctypes.c_int),
+        ("n_best", ctypes.c_uint32),
     ]
 
 
@@ -376,6 +388,19 @@ PROTOTYPES = [
     ("gmm_aligner_posteriors_host", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_float,
       ctypes.c_uint32] + [ctypes.c_void_p] * 8),
+    ("gmm_default_align_search", None, [ctypes.POINTER(AlignSearchStruct)]),
+    ("gmm_aligner_align_search_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(AlignSearchStruct)]
+     + [ctypes.c_void_p] * 8),
+    ("gmm_aligner_align_search_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(AlignSearchStruct)]
+     + [ctypes.c_void_p] * 7),
+    ("gmm_aligner_posteriors_search_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(AlignSearchStruct), ctypes.c_float,
+      ctypes.c_uint32] + [ctypes.c_void_p] * 11),
+    ("gmm_aligner_posteriors_search_host", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(AlignSearchStruct), ctypes.c_float,
+      ctypes.c_uint32] + [ctypes.c_void_p] * 10),
     ("gmm_version", ctypes.c_char_p, []),
     ("gmm_kernel_id", ctypes.c_char_p, []),
 ]

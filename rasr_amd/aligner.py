@@ -12,6 +12,7 @@ A GRAPH here is a dict of numpy arrays describing one segment's automaton, state
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 
 import numpy as np
 
@@ -21,7 +22,25 @@ from ._pairs import ptr as _ptr
 MAX_STATES = _capi.GMM_ALIGN_MAX_STATES
 MAX_STATES_POSTERIOR = _capi.GMM_ALIGN_MAX_STATES_POSTERIOR
 MAX_IN_ARCS = _capi.GMM_ALIGN_MAX_IN_ARCS
+MAX_ITERATIONS = _capi.GMM_ALIGN_MAX_ITERATIONS
 NONE = _capi.GMM_ALIGN_NONE
+
+
+@dataclasses.dataclass
+class AlignSearch:
+    """gmm_align_search: the pruning-threshold search of Search::Aligner::feed and its n-best pruning, with the
+    reference's defaults (include/rasr_gmm_align.h, "THE SEARCH")."""
+    min_pruning: float = 50.0                 # min-acoustic-pruning
+    max_pruning: float = float(np.finfo(np.float32).max)  # max-acoustic-pruning
+    increment_factor: float = 2.0             # acoustic-pruning-increment-factor
+    min_average_hypotheses: float = 0.0       # min-average-number-of-states
+    until_no_score_difference: bool = True    # increase-pruning-until-no-score-difference
+    n_best: int = 0x7FFFFFFF                  # n-best-pruning
+
+    def _struct(self) -> "_capi.AlignSearchStruct":
+        return _capi.AlignSearchStruct(float(self.min_pruning), float(self.max_pruning), float(self.increment_factor),
+                                       float(self.min_average_hypotheses), int(bool(self.until_no_score_difference)),
+                                       int(self.n_best))
 
 
 def linear_hmm_graph(mixtures, loop, forward, skip, exit, repeat: int = 1) -> dict:
@@ -138,8 +157,12 @@ class Aligner:
         self.n_segments = n_segments
 
     def align(self, scores, pruning_threshold: float = float("inf"), n_table_frames=None, out_mixture=None,
-              out_state=None, out_arc=None, stream=None) -> dict:
+              out_state=None, out_arc=None, stream=None, search=None) -> dict:
         """Aligns the batch over `scores`, a [n_mixtures, >= n_table_frames] float32 table.
+
+        With `search` (an AlignSearch) the call is gmm_aligner_align_search_*: every segment runs the reference's
+        threshold schedule and n-best pruning inside the one call, pruning_threshold is ignored, and the result also
+        holds "threshold" [n_segments] float32 (the last pass's) and "iterations" [n_segments] int32.
 
         A torch CUDA tensor: gmm_aligner_align_device, asynchronous on `stream` (a torch stream or a raw handle; default
         the current one); the outputs are CUDA tensors.  A numpy array: gmm_aligner_align_host, synchronous, numpy
@@ -148,7 +171,7 @@ class Aligner:
         tensors allocated here, so the accumulate calls skip them),
         "score" [n_segments] float32 (FLT_MAX without an alignment) and "hypotheses" [n_segments] int32."""
         if isinstance(scores, np.ndarray):
-            return self._align_host(scores, pruning_threshold, n_table_frames, out_mixture, out_state, out_arc)
+            return self._align_host(scores, pruning_threshold, n_table_frames, out_mixture, out_state, out_arc, search)
         import torch
         if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1 or scores.shape[0] != self.n_mixtures:
             raise ValueError("scores must be a float32 [n_mixtures, >= n_table_frames] tensor with unit column stride")
@@ -165,17 +188,29 @@ class Aligner:
         if stream is None:
             stream = torch.cuda.current_stream(scores.device)
         s = getattr(stream, "cuda_stream", stream)
+        out = {"mixture": cols[0], "state": cols[1], "arc": cols[2], "score": score, "hypotheses": hyp}
+        if search is not None:
+            out["threshold"] = torch.empty(self.n_segments, dtype=torch.float32, device=scores.device)
+            out["iterations"] = torch.empty(self.n_segments, dtype=torch.int32, device=scores.device)
+            rc = self._lib.gmm_aligner_align_search_device(
+                self._h, ctypes.c_void_p(scores.data_ptr()), f, int(scores.stride(0)), ctypes.byref(search._struct()),
+                *(ctypes.c_void_p(t.data_ptr()) for t in out.values()), ctypes.c_void_p(s) if s else None)
+            _capi.check(rc, "gmm_aligner_align_search_device")
+            return out
         rc = self._lib.gmm_aligner_align_device(
             self._h, ctypes.c_void_p(scores.data_ptr()), f, int(scores.stride(0)), float(pruning_threshold),
             *(ctypes.c_void_p(t.data_ptr()) for t in cols), ctypes.c_void_p(score.data_ptr()),
             ctypes.c_void_p(hyp.data_ptr()), ctypes.c_void_p(s) if s else None)
         _capi.check(rc, "gmm_aligner_align_device")
-        return {"mixture": cols[0], "state": cols[1], "arc": cols[2], "score": score, "hypotheses": hyp}
+        return out
 
     def posteriors(self, scores, pruning_threshold: float = float("inf"), min_posterior: float = 0.0, max_items=None,
-                   n_table_frames=None, stream=None) -> dict:
+                   n_table_frames=None, stream=None, search=None) -> dict:
         """Baum-Welch alignment of the batch over `scores` (gmm_aligner_posteriors_*): the per-frame mixture posteriors
         as a compact item list ordered by (table column, mixture).
+
+        With `search` (an AlignSearch) the call is gmm_aligner_posteriors_search_*: pruning_threshold is ignored, and the
+        result also holds "threshold" [n_segments] float32 (the last pass's) and "iterations" [n_segments] int32.
 
         Returns {"frame", "mixture"} (int32) and {"weight"} (float64, holding float32 values), trimmed to the number of
         items -- as they stand pair_frame, pair_mixture and pair_weight of Estimator.accumulate_posteriors_device --,
@@ -204,14 +239,21 @@ class Aligner:
         shapes = (("frame", cap, "int32"), ("mixture", cap, "int32"), ("weight", cap, "float64"),
                   ("column_offset", f + 1, "int32"), ("n_items", 1, "int32"), ("score", self.n_segments, "float32"),
                   ("hypotheses", self.n_segments, "int32"), ("log_total", self.n_segments, "float64"))
+        name = "gmm_aligner_posteriors_"
+        if search is not None:
+            shapes += (("threshold", self.n_segments, "float32"), ("iterations", self.n_segments, "int32"))
+            name += "search_"
+            pruning = ctypes.byref(search._struct())
+        else:
+            pruning = float(pruning_threshold)
         if host:
             out = {k: np.zeros(n, dtype=t) for k, n, t in shapes}
-            rc = self._lib.gmm_aligner_posteriors_host(
-                self._h, _ptr(scores), f, scores.shape[1], float(pruning_threshold), float(min_posterior), cap,
+            rc = getattr(self._lib, name + "host")(
+                self._h, _ptr(scores), f, scores.shape[1], pruning, float(min_posterior), cap,
                 *(_ptr(out[k]) for k, _, _ in shapes))
             n = int(out["n_items"][0])
             try:
-                _capi.check(rc, "gmm_aligner_posteriors_host")
+                _capi.check(rc, name + "host")
             except _capi.GmmError as err:
                 err.n_items = n  # exact when the code is GMM_ERR_CAPACITY
                 raise
@@ -220,11 +262,11 @@ class Aligner:
             if stream is None:
                 stream = torch.cuda.current_stream(scores.device)
             s = getattr(stream, "cuda_stream", stream)
-            rc = self._lib.gmm_aligner_posteriors_device(
-                self._h, ctypes.c_void_p(scores.data_ptr()), f, int(scores.stride(0)), float(pruning_threshold),
+            rc = getattr(self._lib, name + "device")(
+                self._h, ctypes.c_void_p(scores.data_ptr()), f, int(scores.stride(0)), pruning,
                 float(min_posterior), cap, *(ctypes.c_void_p(out[k].data_ptr()) for k, _, _ in shapes),
                 ctypes.c_void_p(s) if s else None)
-            _capi.check(rc, "gmm_aligner_posteriors_device")
+            _capi.check(rc, name + "device")
             n = int(out["n_items"].item())  # the one synchronisation
             if n > cap:
                 err = _capi.GmmError(f"gmm_aligner_posteriors_device: the call produces {n} items, more than max_items "
@@ -236,7 +278,7 @@ class Aligner:
         out["n_items"] = n
         return out
 
-    def _align_host(self, scores, pruning_threshold, n_table_frames, out_mixture, out_state, out_arc) -> dict:
+    def _align_host(self, scores, pruning_threshold, n_table_frames, out_mixture, out_state, out_arc, search=None) -> dict:
         scores = np.ascontiguousarray(scores, dtype=np.float32)
         if scores.ndim != 2 or scores.shape[0] != self.n_mixtures:
             raise ValueError("scores must be [n_mixtures, >= n_table_frames]")
@@ -250,7 +292,15 @@ class Aligner:
             cols.append(t)
         score = np.empty(self.n_segments, dtype=np.float32)
         hyp = np.empty(self.n_segments, dtype=np.int32)
+        out = {"mixture": cols[0], "state": cols[1], "arc": cols[2], "score": score, "hypotheses": hyp}
+        if search is not None:
+            out["threshold"] = np.empty(self.n_segments, dtype=np.float32)
+            out["iterations"] = np.empty(self.n_segments, dtype=np.int32)
+            rc = self._lib.gmm_aligner_align_search_host(self._h, _ptr(scores), f, scores.shape[1],
+                                                         ctypes.byref(search._struct()), *map(_ptr, out.values()))
+            _capi.check(rc, "gmm_aligner_align_search_host")
+            return out
         rc = self._lib.gmm_aligner_align_host(self._h, _ptr(scores), f, scores.shape[1], float(pruning_threshold),
                                               *map(_ptr, cols), _ptr(score), _ptr(hyp))
         _capi.check(rc, "gmm_aligner_align_host")
-        return {"mixture": cols[0], "state": cols[1], "arc": cols[2], "score": score, "hypotheses": hyp}
+        return out

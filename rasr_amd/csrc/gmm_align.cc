@@ -1,6 +1,8 @@
 // gmm_align.cc -- the handle behind include/rasr_gmm_align.h: its device memory (the batch's tables and the
 // backpointer scratch, all allocated at creation), set_segments (host/AlignGraph.cc validates and builds, this unit
 // uploads), the checks and the launch of an align call (gmm_kernels_align.hip), the host call's staging.
+#include <cfloat>
+#include <cmath>
 #include <memory>
 #include <new>
 
@@ -90,8 +92,53 @@ int checkAlignCall(const gmm_aligner* h, const float* scores, uint32_t nTableFra
     return GMM_OK;
 }
 
+// the search outputs of a search call; search == nullptr: the fixed-threshold call
+struct SearchCall {
+    const AlignSearch* search        = nullptr;
+    float*             outThreshold  = nullptr;
+    uint32_t*          outIterations = nullptr;
+};
+
+// The checks of gmm_align_search, before anything is written; fills `out`.  The schedule is counted with the f32
+// multiply the kernels use.
+int checkSearch(const gmm_align_search* s, AlignSearch& out) {
+    if (!s)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: null search");
+    if (std::isnan(s->min_pruning) || std::isnan(s->max_pruning) || std::isnan(s->increment_factor) ||
+        std::isnan(s->min_average_hypotheses))
+        return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: a NaN in the search");
+    if (s->min_pruning < FLT_MIN)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: min_pruning below FLT_MIN");
+    if (!std::isfinite(s->max_pruning))
+        return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: max_pruning is not finite");
+    if (s->min_pruning > s->max_pruning)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: min_pruning above max_pruning");
+    if (s->increment_factor <= 1.0f && s->min_pruning != s->max_pruning)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: increment_factor <= 1 with min_pruning != max_pruning");
+    if (s->n_best == 0)
+        return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: n_best 0");
+    if (s->increment_factor > 1.0f) {
+        uint32_t       count = 0;
+        volatile float t = s->min_pruning;  // volatile: one f32 rounding per step whatever the host's evaluation method
+        while (t <= s->max_pruning && count <= GMM_ALIGN_MAX_ITERATIONS) {
+            ++count;
+            t = t * s->increment_factor;
+        }
+        if (count > GMM_ALIGN_MAX_ITERATIONS)
+            return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: a schedule of more than GMM_ALIGN_MAX_ITERATIONS thresholds");
+    }
+    out.minPruning        = s->min_pruning;
+    out.maxPruning        = s->max_pruning;
+    out.factor            = s->increment_factor;
+    out.minAverage        = s->min_average_hypotheses;
+    out.untilNoDifference = s->until_no_score_difference != 0;
+    out.nBest             = s->n_best;
+    return GMM_OK;
+}
+
 int alignOn(gmm_aligner* h, const float* scores, uint32_t scoreStride, float pruning, uint32_t* outMixture,
-            uint32_t* outState, uint32_t* outArc, float* outScore, uint32_t* outHypotheses, hipStream_t stream) {
+            uint32_t* outState, uint32_t* outArc, float* outScore, uint32_t* outHypotheses, hipStream_t stream,
+            const SearchCall& sc = SearchCall{}) {
     AlignArgs a{};
     a.segments      = h->dSegments.get();
     a.order         = h->dOrder.get();
@@ -112,7 +159,8 @@ int alignOn(gmm_aligner* h, const float* scores, uint32_t scoreStride, float pru
     a.outHypotheses = outHypotheses;
     a.nSegments     = h->nSegments;
     a.rowStates     = h->rowStates;
-    const hipError_t e = launchAlign(a, stream);
+    const hipError_t e = sc.search ? launchAlignSearch(AlignSearchArgs{a, *sc.search, sc.outThreshold, sc.outIterations}, stream)
+                                   : launchAlign(a, stream);
     // what was enqueued uses the handle's tables and scratch
     GMM_HIP_CHECK(hipEventRecord(h->done.get(), stream));
     h->pending = true;
@@ -206,7 +254,7 @@ int checkPosteriorCall(const gmm_aligner* h, const float* scores, uint32_t nTabl
 int posteriorsOn(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride, float pruning,
                  float minPosterior, uint32_t maxItems, uint32_t* itemFrame, uint32_t* itemMixture, double* itemWeight,
                  uint32_t* columnOffset, uint32_t* nItems, float* outScore, uint32_t* outHypotheses, double* logTotal,
-                 hipStream_t stream) {
+                 hipStream_t stream, const SearchCall& sc = SearchCall{}) {
     const int rc = preparePosterior(h);
     if (rc != GMM_OK)
         return rc;
@@ -257,7 +305,10 @@ int posteriorsOn(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uin
     a.nSegments       = h->nSegments;
     a.rowStates       = h->rowStates;
     a.nFrames         = static_cast<uint32_t>(h->posterior.nFrames);
-    const hipError_t e = launchAlignPosteriors(a, stream);
+    const hipError_t e =
+            sc.search ? launchAlignPosteriorsSearch(AlignPosteriorSearchArgs{a, *sc.search, sc.outThreshold, sc.outIterations},
+                                                    stream)
+                      : launchAlignPosteriors(a, stream);
     GMM_HIP_CHECK(hipEventRecord(h->done.get(), stream));
     h->pending = true;
     GMM_HIP_CHECK(e);
@@ -347,25 +398,33 @@ int gmm_aligner_align_device(gmm_aligner* h, const float* scores, uint32_t nTabl
                    static_cast<hipStream_t>(stream));
 }
 
-int gmm_aligner_align_host(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride, float pruning,
-                           uint32_t* outMixture, uint32_t* outState, uint32_t* outArc, float* outScore,
-                           uint32_t* outHypotheses) {
-    int rc = checkAlignCall(h, scores, nTableFrames, scoreStride, outMixture, outState, outArc, outScore, outHypotheses);
-    if (rc != GMM_OK)
-        return rc;
+// the staging of both host align calls, behind their checks; hs: the search with its HOST outputs
+static int alignHost(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride, float pruning,
+                     uint32_t* outMixture, uint32_t* outState, uint32_t* outArc, float* outScore, uint32_t* outHypotheses,
+                     const SearchCall& hs) {
+    int rc;
     GMM_HIP_CHECK(hipSetDevice(h->device));
     if ((rc = waitDone(h)) != GMM_OK)
         return rc;
     // the table, dense; the per-column outputs start from the host arrays, whose columns of no segment are kept
     const size_t           F = nTableFrames, M = h->cap.nMixtures, S = h->nSegments;
-    DeviceBuffer<float>    dTable, dScore;
-    DeviceBuffer<uint32_t> dColumns, dHypotheses;  // dColumns: mixture, state, arc
+    DeviceBuffer<float>    dTable, dScore, dThreshold;
+    DeviceBuffer<uint32_t> dColumns, dHypotheses, dIterations;  // dColumns: mixture, state, arc
     uint32_t* const        host[3] = {outMixture, outState, outArc};
     uint32_t*              dev[3]  = {nullptr, nullptr, nullptr};
     GMM_HIP_CHECK(dTable.alloc(M * F));
     GMM_HIP_CHECK(dColumns.alloc(3 * F));
     GMM_HIP_CHECK(dScore.alloc(S));
     GMM_HIP_CHECK(dHypotheses.alloc(S));
+    SearchCall sc = hs;
+    if (hs.outThreshold) {
+        GMM_HIP_CHECK(dThreshold.alloc(S));
+        sc.outThreshold = dThreshold.get();
+    }
+    if (hs.outIterations) {
+        GMM_HIP_CHECK(dIterations.alloc(S));
+        sc.outIterations = dIterations.get();
+    }
     if (F)
         GMM_HIP_CHECK(hipMemcpy2D(dTable.get(), F * sizeof(float), scores, static_cast<size_t>(scoreStride) * sizeof(float),
                                   F * sizeof(float), M, hipMemcpyHostToDevice));
@@ -375,7 +434,7 @@ int gmm_aligner_align_host(gmm_aligner* h, const float* scores, uint32_t nTableF
             GMM_HIP_CHECK(hipMemcpy(dev[o], host[o], F * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
     rc = alignOn(h, dTable.get(), nTableFrames, pruning, dev[0], dev[1], dev[2], outScore ? dScore.get() : nullptr,
-                 outHypotheses ? dHypotheses.get() : nullptr, nullptr);
+                 outHypotheses ? dHypotheses.get() : nullptr, nullptr, sc);
     if (rc != GMM_OK) {
         (void)hipStreamSynchronize(nullptr);  // the buffers go with this scope
         return rc;
@@ -388,8 +447,62 @@ int gmm_aligner_align_host(gmm_aligner* h, const float* scores, uint32_t nTableF
         GMM_HIP_CHECK(hipMemcpy(outScore, dScore.get(), S * sizeof(float), hipMemcpyDeviceToHost));
     if (outHypotheses)
         GMM_HIP_CHECK(hipMemcpy(outHypotheses, dHypotheses.get(), S * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (hs.outThreshold)
+        GMM_HIP_CHECK(hipMemcpy(hs.outThreshold, dThreshold.get(), S * sizeof(float), hipMemcpyDeviceToHost));
+    if (hs.outIterations)
+        GMM_HIP_CHECK(hipMemcpy(hs.outIterations, dIterations.get(), S * sizeof(uint32_t), hipMemcpyDeviceToHost));
     GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
     return GMM_OK;
+}
+
+int gmm_aligner_align_host(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride, float pruning,
+                           uint32_t* outMixture, uint32_t* outState, uint32_t* outArc, float* outScore,
+                           uint32_t* outHypotheses) {
+    const int rc = checkAlignCall(h, scores, nTableFrames, scoreStride, outMixture, outState, outArc, outScore, outHypotheses);
+    if (rc != GMM_OK)
+        return rc;
+    return alignHost(h, scores, nTableFrames, scoreStride, pruning, outMixture, outState, outArc, outScore, outHypotheses,
+                     SearchCall{});
+}
+
+void gmm_default_align_search(gmm_align_search* s) {
+    if (!s)
+        return;
+    s->min_pruning               = 50.0f;
+    s->max_pruning               = FLT_MAX;
+    s->increment_factor          = 2.0f;
+    s->min_average_hypotheses    = 0.0;
+    s->until_no_score_difference = 1;
+    s->n_best                    = 0x7fffffffu;
+}
+
+int gmm_aligner_align_search_device(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
+                                    const gmm_align_search* search, uint32_t* outMixture, uint32_t* outState,
+                                    uint32_t* outArc, float* outScore, uint32_t* outHypotheses, float* outThreshold,
+                                    uint32_t* outIterations, void* stream) {
+    int rc = checkAlignCall(h, scores, nTableFrames, scoreStride, outMixture, outState, outArc, outScore, outHypotheses);
+    if (rc != GMM_OK)
+        return rc;
+    AlignSearch as{};
+    if ((rc = checkSearch(search, as)) != GMM_OK)
+        return rc;
+    GMM_HIP_CHECK(hipSetDevice(h->device));
+    return alignOn(h, scores, scoreStride, 0.0f, outMixture, outState, outArc, outScore, outHypotheses,
+                   static_cast<hipStream_t>(stream), SearchCall{&as, outThreshold, outIterations});
+}
+
+int gmm_aligner_align_search_host(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
+                                  const gmm_align_search* search, uint32_t* outMixture, uint32_t* outState,
+                                  uint32_t* outArc, float* outScore, uint32_t* outHypotheses, float* outThreshold,
+                                  uint32_t* outIterations) {
+    int rc = checkAlignCall(h, scores, nTableFrames, scoreStride, outMixture, outState, outArc, outScore, outHypotheses);
+    if (rc != GMM_OK)
+        return rc;
+    AlignSearch as{};
+    if ((rc = checkSearch(search, as)) != GMM_OK)
+        return rc;
+    return alignHost(h, scores, nTableFrames, scoreStride, 0.0f, outMixture, outState, outArc, outScore, outHypotheses,
+                     SearchCall{&as, outThreshold, outIterations});
 }
 
 int gmm_aligner_posteriors_device(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
@@ -406,21 +519,28 @@ int gmm_aligner_posteriors_device(gmm_aligner* h, const float* scores, uint32_t 
                         static_cast<hipStream_t>(stream));
 }
 
-int gmm_aligner_posteriors_host(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
-                                float pruning, float minPosterior, uint32_t maxItems, uint32_t* itemFrame,
-                                uint32_t* itemMixture, double* itemWeight, uint32_t* columnOffset, uint32_t* nItems,
-                                float* outScore, uint32_t* outHypotheses, double* logTotal) {
-    int rc = checkPosteriorCall(h, scores, nTableFrames, scoreStride, maxItems, itemFrame, itemMixture, itemWeight,
-                                columnOffset, nItems, outScore, outHypotheses, logTotal);
-    if (rc != GMM_OK)
-        return rc;
+// the staging of both host posterior calls, behind their checks; hs: the search with its HOST outputs
+static int posteriorsHost(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride, float pruning,
+                          float minPosterior, uint32_t maxItems, uint32_t* itemFrame, uint32_t* itemMixture,
+                          double* itemWeight, uint32_t* columnOffset, uint32_t* nItems, float* outScore,
+                          uint32_t* outHypotheses, double* logTotal, const SearchCall& hs) {
+    int rc;
     GMM_HIP_CHECK(hipSetDevice(h->device));
     if ((rc = waitDone(h)) != GMM_OK)
         return rc;
     const size_t           F = nTableFrames, M = h->cap.nMixtures, S = h->nSegments, I = itemFrame ? maxItems : 0;
-    DeviceBuffer<float>    dTable, dScore;
-    DeviceBuffer<uint32_t> dItems, dColumnOffset, dCount, dHypotheses;  // dItems: frame, mixture
+    DeviceBuffer<float>    dTable, dScore, dThreshold;
+    DeviceBuffer<uint32_t> dItems, dColumnOffset, dCount, dHypotheses, dIterations;  // dItems: frame, mixture
     DeviceBuffer<double>   dWeight, dLogTotal;
+    SearchCall             sc = hs;
+    if (hs.outThreshold) {
+        GMM_HIP_CHECK(dThreshold.alloc(S));
+        sc.outThreshold = dThreshold.get();
+    }
+    if (hs.outIterations) {
+        GMM_HIP_CHECK(dIterations.alloc(S));
+        sc.outIterations = dIterations.get();
+    }
     GMM_HIP_CHECK(dTable.alloc(M * F));
     GMM_HIP_CHECK(dItems.alloc(2 * I));
     GMM_HIP_CHECK(dWeight.alloc(I));
@@ -435,7 +555,7 @@ int gmm_aligner_posteriors_host(gmm_aligner* h, const float* scores, uint32_t nT
     rc = posteriorsOn(h, dTable.get(), nTableFrames, nTableFrames, pruning, minPosterior, maxItems,
                       I ? dItems.get() : nullptr, I ? dItems.get() + I : nullptr, I ? dWeight.get() : nullptr,
                       columnOffset ? dColumnOffset.get() : nullptr, dCount.get(), outScore ? dScore.get() : nullptr,
-                      outHypotheses ? dHypotheses.get() : nullptr, logTotal ? dLogTotal.get() : nullptr, nullptr);
+                      outHypotheses ? dHypotheses.get() : nullptr, logTotal ? dLogTotal.get() : nullptr, nullptr, sc);
     if (rc != GMM_OK) {
         (void)hipStreamSynchronize(nullptr);  // the buffers go with this scope
         return rc;
@@ -450,6 +570,10 @@ int gmm_aligner_posteriors_host(gmm_aligner* h, const float* scores, uint32_t nT
         GMM_HIP_CHECK(hipMemcpy(outHypotheses, dHypotheses.get(), S * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (logTotal)
         GMM_HIP_CHECK(hipMemcpy(logTotal, dLogTotal.get(), S * sizeof(double), hipMemcpyDeviceToHost));
+    if (hs.outThreshold)
+        GMM_HIP_CHECK(hipMemcpy(hs.outThreshold, dThreshold.get(), S * sizeof(float), hipMemcpyDeviceToHost));
+    if (hs.outIterations)
+        GMM_HIP_CHECK(hipMemcpy(hs.outIterations, dIterations.get(), S * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (I && count > maxItems) {
         GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
         return fail(GMM_ERR_CAPACITY, "aligner: the call produces " + std::to_string(count) + " items, more than max_items " +
@@ -464,6 +588,53 @@ int gmm_aligner_posteriors_host(gmm_aligner* h, const float* scores, uint32_t nT
         GMM_HIP_CHECK(hipMemcpy(columnOffset, dColumnOffset.get(), (F + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
     return GMM_OK;
+}
+
+int gmm_aligner_posteriors_host(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
+                                float pruning, float minPosterior, uint32_t maxItems, uint32_t* itemFrame,
+                                uint32_t* itemMixture, double* itemWeight, uint32_t* columnOffset, uint32_t* nItems,
+                                float* outScore, uint32_t* outHypotheses, double* logTotal) {
+    const int rc = checkPosteriorCall(h, scores, nTableFrames, scoreStride, maxItems, itemFrame, itemMixture, itemWeight,
+                                      columnOffset, nItems, outScore, outHypotheses, logTotal);
+    if (rc != GMM_OK)
+        return rc;
+    return posteriorsHost(h, scores, nTableFrames, scoreStride, pruning, minPosterior, maxItems, itemFrame, itemMixture,
+                          itemWeight, columnOffset, nItems, outScore, outHypotheses, logTotal, SearchCall{});
+}
+
+int gmm_aligner_posteriors_search_device(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
+                                         const gmm_align_search* search, float minPosterior, uint32_t maxItems,
+                                         uint32_t* itemFrame, uint32_t* itemMixture, double* itemWeight,
+                                         uint32_t* columnOffset, uint32_t* nItems, float* outScore, uint32_t* outHypotheses,
+                                         double* logTotal, float* outThreshold, uint32_t* outIterations, void* stream) {
+    int rc = checkPosteriorCall(h, scores, nTableFrames, scoreStride, maxItems, itemFrame, itemMixture, itemWeight,
+                                columnOffset, nItems, outScore, outHypotheses, logTotal);
+    if (rc != GMM_OK)
+        return rc;
+    AlignSearch as{};
+    if ((rc = checkSearch(search, as)) != GMM_OK)
+        return rc;
+    GMM_HIP_CHECK(hipSetDevice(h->device));
+    return posteriorsOn(h, scores, nTableFrames, scoreStride, 0.0f, minPosterior, maxItems, itemFrame, itemMixture,
+                        itemWeight, columnOffset, nItems, outScore, outHypotheses, logTotal,
+                        static_cast<hipStream_t>(stream), SearchCall{&as, outThreshold, outIterations});
+}
+
+int gmm_aligner_posteriors_search_host(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
+                                       const gmm_align_search* search, float minPosterior, uint32_t maxItems,
+                                       uint32_t* itemFrame, uint32_t* itemMixture, double* itemWeight,
+                                       uint32_t* columnOffset, uint32_t* nItems, float* outScore, uint32_t* outHypotheses,
+                                       double* logTotal, float* outThreshold, uint32_t* outIterations) {
+    int rc = checkPosteriorCall(h, scores, nTableFrames, scoreStride, maxItems, itemFrame, itemMixture, itemWeight,
+                                columnOffset, nItems, outScore, outHypotheses, logTotal);
+    if (rc != GMM_OK)
+        return rc;
+    AlignSearch as{};
+    if ((rc = checkSearch(search, as)) != GMM_OK)
+        return rc;
+    return posteriorsHost(h, scores, nTableFrames, scoreStride, 0.0f, minPosterior, maxItems, itemFrame, itemMixture,
+                          itemWeight, columnOffset, nItems, outScore, outHypotheses, logTotal,
+                          SearchCall{&as, outThreshold, outIterations});
 }
 
 }  // extern "C"

@@ -40,6 +40,24 @@ struct AlignArgs {
 
 hipError_t launchAlign(const AlignArgs& a, hipStream_t stream);
 
+// The search calls (gmm_aligner_*_search_*): gmm_align_search as the kernels read it, and the two outputs it adds.  The
+// kernels of the fixed-threshold calls keep their argument structs; the search kernels take them wrapped, and ignore
+// their `pruning`
+struct AlignSearch {
+    float    minPruning, maxPruning, factor;
+    double   minAverage;
+    uint32_t untilNoDifference, nBest;
+};
+
+struct AlignSearchArgs {
+    AlignArgs   call;
+    AlignSearch search;
+    float*      outThreshold;   // [nSegments] or NULL
+    uint32_t*   outIterations;  // [nSegments] or NULL
+};
+
+hipError_t launchAlignSearch(const AlignSearchArgs& a, hipStream_t stream);
+
 // The Baum-Welch call (gmm_kernels_align_posterior.hip).  LDS of a segment's workgroup: two f64 potential rows, two f32
 // score rows and two rows of active marks (GMM_ALIGN_MAX_STATES_POSTERIOR); the rows are rounded up to 64 states
 constexpr uint32_t kAlignPosteriorLdsBytesPerState = 2 * (sizeof(double) + sizeof(float) + 1);
@@ -87,5 +105,15 @@ struct AlignPosteriorArgs {
 };
 
 hipError_t launchAlignPosteriors(const AlignPosteriorArgs& a, hipStream_t stream);
+
+struct AlignPosteriorSearchArgs {
+    AlignPosteriorArgs call;
+    AlignSearch        search;
+    float*             outThreshold;
+    uint32_t*          outIterations;
+};
+
+// the sweep with the retry loop and the n-best step, then the item launches of launchAlignPosteriors as they are
+hipError_t launchAlignPosteriorsSearch(const AlignPosteriorSearchArgs& a, hipStream_t stream);
 
 }  // namespace rasr_gmm

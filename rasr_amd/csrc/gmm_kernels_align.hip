@@ -22,7 +22,11 @@
 // one dependent load per frame, and leaves (ordinal, state) of frame t in the frame's cell 0; all lanes then resolve
 // these to the arc, its mixture and its target and write the outputs.
 // Every floating-point operation is an _rn intrinsic (the unit is also built with -ffp-contract=off).
+// alignViterbiSearch (gmm_aligner_align_search_*) is the same segment function with the search flag on: the retry loop
+// of feed(vector) around the frame loop, the n-best step of gmm_align_search.hh in the prune; alignViterbi's code does
+// not change with it.
 #include "gmm_align.hh"
+#include "gmm_align_search.hh"
 
 #include <cfloat>
 
@@ -60,108 +64,165 @@ __device__ __forceinline__ void finalStep(float& v, uint32_t& q, float v2, uint3
     q               = take ? q2 : q;
 }
 
-template <bool kWave>
+// kSearch: the pass below runs inside the retry loop of feed(vector), with the n-best step in its prune; without it the
+// function is the one pass at a.pruning
+template <bool kWave, bool kSearch>
 __device__ __forceinline__ void alignSegment(const AlignArgs& a, const uint32_t segment, float* rows, uint8_t* marks,
-                                             float* redV, uint32_t* redQ) {
+                                             float* redV, uint32_t* redQ, const SearchContext& sc) {
     constexpr uint32_t T   = kWave ? 64u : kAlignThreads;
     const AlignSegment sg  = a.segments[segment];
     const uint32_t     tid = threadIdx.x, n = sg.nStates, gb = sg.stateBegin;
     const uint32_t     wave = tid >> 6, lane = tid & 63u;
     uint32_t* const    cells = a.cells + sg.cellBegin;
+    float              pruning = a.pruning, previous = FLT_MAX, best;
+    uint32_t           iterations = 0, bestState, hypotheses;
+    if constexpr (kSearch)
+        pruning = sc.search->minPruning;
 
-    // start: the initial state alone, with score 0
-    for (uint32_t q = tid; q < n; q += T) {
-        rows[q]  = 0.0f;
-        marks[q] = q == sg.initial;
-    }
-    sync<kWave>();
-
-    uint32_t hypotheses = 0;
-    for (uint32_t t = 0; t < sg.nFrames; ++t) {
-        const uint32_t       from = (t & 1u) * a.rowStates, to = ((t & 1u) ^ 1u) * a.rowStates;
-        const float* const   prev = rows + from;
-        const uint8_t* const prevMark = marks + from;
-        float* const         cur = rows + to;
-        uint8_t* const       curMark = marks + to;
-        const float* const   column = a.scores + sg.frameBegin + t;
-        uint32_t* const      back = cells + static_cast<size_t>(t) * n;
-        float                mn = FLT_MAX;
+    for (;;) {  // the passes of the search; one without it
+        // start: the initial state alone, with score 0
         for (uint32_t q = tid; q < n; q += T) {
-            const uint32_t j0 = a.inOffset[gb + q], j1 = a.inOffset[gb + q + 1];
-            bool           reached = false;
-            float          score = 0.0f;
-            uint32_t       bp = 0;
-            for (uint32_t j = j0; j < j1; ++j) {
-                const uint32_t p = a.inSource[j];
-                const float    w = a.inWeight[j];
-                const float    e = column[static_cast<size_t>(a.inMixture[j]) * a.scoreStride];
-                if (prevMark[p]) {
-                    const float cand = __fadd_rn(__fadd_rn(prev[p], w), e);
-                    if (!reached || score >= cand) {
-                        score = cand;
-                        bp    = ((j - j0) << 16) | p;
+            rows[q]  = 0.0f;
+            marks[q] = q == sg.initial;
+        }
+        sync<kWave>();
+
+        hypotheses = 0;
+        for (uint32_t t = 0; t < sg.nFrames; ++t) {
+            const uint32_t       from = (t & 1u) * a.rowStates, to = ((t & 1u) ^ 1u) * a.rowStates;
+            const float* const   prev = rows + from;
+            const uint8_t* const prevMark = marks + from;
+            float* const         cur = rows + to;
+            uint8_t* const       curMark = marks + to;
+            const float* const   column = a.scores + sg.frameBegin + t;
+            uint32_t* const      back = cells + static_cast<size_t>(t) * n;
+            float                mn = FLT_MAX;
+            uint32_t             nReached = 0;  // kSearch only
+            for (uint32_t q = tid; q < n; q += T) {
+                const uint32_t j0 = a.inOffset[gb + q], j1 = a.inOffset[gb + q + 1];
+                bool           reached = false;
+                float          score = 0.0f;
+                uint32_t       bp = 0;
+                for (uint32_t j = j0; j < j1; ++j) {
+                    const uint32_t p = a.inSource[j];
+                    const float    w = a.inWeight[j];
+                    const float    e = column[static_cast<size_t>(a.inMixture[j]) * a.scoreStride];
+                    if (prevMark[p]) {
+                        const float cand = __fadd_rn(__fadd_rn(prev[p], w), e);
+                        if (!reached || score >= cand) {
+                            score = cand;
+                            bp    = ((j - j0) << 16) | p;
+                        }
+                        reached = true;
                     }
-                    reached = true;
+                }
+                cur[q]     = score;
+                curMark[q] = reached;
+                back[q]    = bp;
+                if (reached)
+                    mn = minStep(mn, score);
+                if constexpr (kSearch)
+                    nReached += reached;
+            }
+            for (uint32_t d = 32; d; d >>= 1) {
+                mn = minStep(mn, __shfl_xor(mn, d));
+                if constexpr (kSearch)
+                    nReached += __shfl_xor(nReached, d);
+            }
+            if constexpr (!kWave) {
+                if (lane == 0) {
+                    redV[wave] = mn;
+                    if constexpr (kSearch)
+                        sc.lds->reached[wave] = nReached;
+                }
+                __syncthreads();
+                mn = FLT_MAX;
+                for (uint32_t w = 0; w < kWaves; ++w)
+                    mn = minStep(mn, redV[w]);
+                if constexpr (kSearch) {
+                    nReached = 0;
+                    for (uint32_t w = 0; w < kWaves; ++w)
+                        nReached += sc.lds->reached[w];
                 }
             }
-            cur[q]     = score;
-            curMark[q] = reached;
-            back[q]    = bp;
-            if (reached)
-                mn = minStep(mn, score);
-        }
-        for (uint32_t d = 32; d; d >>= 1)
-            mn = minStep(mn, __shfl_xor(mn, d));
-        if constexpr (!kWave) {
-            if (lane == 0)
-                redV[wave] = mn;
-            __syncthreads();
-            mn = FLT_MAX;
-            for (uint32_t w = 0; w < kWaves; ++w)
-                mn = minStep(mn, redV[w]);
-        }
-        const float threshold = __fadd_rn(mn, a.pruning);
-        for (uint32_t q = tid; q < n; q += T)
-            if (curMark[q]) {
-                const bool keep = cur[q] <= threshold;
-                curMark[q]      = keep;
-                hypotheses += keep;
+            const float threshold = __fadd_rn(mn, pruning);
+            if constexpr (kSearch) {
+                // uniform over the workgroup: every lane holds the same count
+                if (sc.search->nBest < nReached)
+                    nBestStep<kWave>(cur, curMark, n, sc.search->nBest, __fadd_rn(threshold, 1.0f), *sc.lds);
             }
-        sync<kWave>();
-    }
+            for (uint32_t q = tid; q < n; q += T)
+                if (curMark[q]) {
+                    const bool keep = cur[q] <= threshold;
+                    curMark[q]      = keep;
+                    hypotheses += keep;
+                }
+            sync<kWave>();
+        }
 
-    // the final scan over the active states of the last frame
-    const uint32_t last = (sg.nFrames & 1u) * a.rowStates;
-    float          best = FLT_MAX;
-    uint32_t       bestState = kNone;
-    for (uint32_t q = tid; q < n; q += T)
-        if (marks[last + q]) {
-            const float v = __fadd_rn(a.finalWeight[gb + q], rows[last + q]);
-            if (v < best) {
-                best      = v;
-                bestState = q;
+        // the final scan over the active states of the last frame
+        const uint32_t last = (sg.nFrames & 1u) * a.rowStates;
+        best      = FLT_MAX;
+        bestState = kNone;
+        for (uint32_t q = tid; q < n; q += T)
+            if (marks[last + q]) {
+                const float v = __fadd_rn(a.finalWeight[gb + q], rows[last + q]);
+                if (v < best) {
+                    best      = v;
+                    bestState = q;
+                }
+            }
+        for (uint32_t d = 32; d; d >>= 1) {
+            const float    v2 = __shfl_xor(best, d);
+            const uint32_t q2 = __shfl_xor(bestState, d);
+            finalStep(best, bestState, v2, q2);
+            hypotheses += __shfl_xor(hypotheses, d);
+        }
+        if constexpr (!kWave) {
+            // redV's last readers are behind the last frame's second barrier
+            if (lane == 0) {
+                redV[wave]          = best;
+                redQ[wave]          = bestState;
+                redQ[kWaves + wave] = hypotheses;
+            }
+            __syncthreads();
+            best       = FLT_MAX;
+            bestState  = kNone;
+            hypotheses = 0;
+            for (uint32_t w = 0; w < kWaves; ++w) {
+                finalStep(best, bestState, redV[w], redQ[w]);
+                hypotheses += redQ[kWaves + w];
             }
         }
-    for (uint32_t d = 32; d; d >>= 1) {
-        const float    v2 = __shfl_xor(best, d);
-        const uint32_t q2 = __shfl_xor(bestState, d);
-        finalStep(best, bestState, v2, q2);
-        hypotheses += __shfl_xor(hypotheses, d);
-    }
-    if constexpr (!kWave) {
-        // redV's last readers are behind the last frame's second barrier
-        if (lane == 0) {
-            redV[wave]          = best;
-            redQ[wave]          = bestState;
-            redQ[kWaves + wave] = hypotheses;
-        }
-        __syncthreads();
-        best       = FLT_MAX;
-        bestState  = kNone;
-        hypotheses = 0;
-        for (uint32_t w = 0; w < kWaves; ++w) {
-            finalStep(best, bestState, redV[w], redQ[w]);
-            hypotheses += redQ[kWaves + w];
+        if constexpr (!kSearch) {
+            break;
+        } else {
+            // the pass is over: every lane holds its score and hypothesis count.  One wave decides in every lane alike;
+            // in the workgroup form lane 0 does and hands the verdict over in LDS.  The next pass overwrites the
+            // backpointers
+            const float at = pruning;
+            ++iterations;
+            bool stop;
+            if constexpr (kWave) {
+                stop = searchStops(*sc.search, best, hypotheses, sg.nFrames, iterations, previous, pruning);
+            } else {
+                if (tid == 0)
+                    sc.lds->stop = searchStops(*sc.search, best, hypotheses, sg.nFrames, iterations, previous, pruning);
+                __syncthreads();
+                stop = sc.lds->stop != 0;
+                // lane 0's next threshold is one f32 product of values every lane holds
+                if (!stop && tid != 0)
+                    pruning = __fmul_rn(pruning, sc.search->factor);
+            }
+            if (stop) {
+                if (tid == 0) {
+                    if (sc.outThreshold)
+                        sc.outThreshold[segment] = at;
+                    if (sc.outIterations)
+                        sc.outIterations[segment] = iterations;
+                }
+                break;
+            }
         }
     }
     if (tid == 0) {
@@ -221,9 +282,35 @@ __global__ __launch_bounds__(kAlignThreads) void alignViterbi(AlignArgs a) {
     // uniform over the workgroup: either wave 0 alone, with no barrier, or all waves through every barrier
     if (a.segments[segment].nStates <= kAlignWaveStates) {
         if (threadIdx.x < 64)
-            alignSegment<true>(a, segment, rows, marks, redV, redQ);
+            alignSegment<true, false>(a, segment, rows, marks, redV, redQ, SearchContext{});
     } else {
-        alignSegment<false>(a, segment, rows, marks, redV, redQ);
+        alignSegment<false, false>(a, segment, rows, marks, redV, redQ, SearchContext{});
+    }
+}
+
+// the search call: the same workgroup per segment, each with its own number of passes
+__global__ __launch_bounds__(kAlignThreads) void alignViterbiSearch(AlignSearchArgs sa) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    __shared__ float     redV[kWaves];
+    __shared__ uint32_t  redQ[2 * kWaves];
+    __shared__ SearchLds searchLds;
+    static_assert(GMM_ALIGN_MAX_STATES * kAlignLdsBytesPerState + sizeof(redV) + sizeof(redQ) + sizeof(SearchLds) +
+                                  2 * kLdsAlign <= kLdsBytes,
+                  "the rows of the largest segment fit beside all static LDS of the search kernel");
+    const AlignArgs&     a = sa.call;
+    float* const         rows  = reinterpret_cast<float*>(lds);
+    uint8_t* const       marks = lds + 2u * a.rowStates * sizeof(float);
+    const uint32_t       segment = a.order[blockIdx.x];
+    SearchContext        sc;
+    sc.search        = &sa.search;
+    sc.outThreshold  = sa.outThreshold;
+    sc.outIterations = sa.outIterations;
+    sc.lds           = &searchLds;
+    if (a.segments[segment].nStates <= kAlignWaveStates) {
+        if (threadIdx.x < 64)
+            alignSegment<true, true>(a, segment, rows, marks, redV, redQ, sc);
+    } else {
+        alignSegment<false, true>(a, segment, rows, marks, redV, redQ, sc);
     }
 }
 
@@ -234,6 +321,14 @@ hipError_t launchAlign(const AlignArgs& a, hipStream_t stream) {
         return hipSuccess;
     const size_t ldsBytes = static_cast<size_t>(a.rowStates) * kAlignLdsBytesPerState;
     hipLaunchKernelGGL(dev::alignViterbi, dim3(a.nSegments), dim3(kAlignThreads), ldsBytes, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launchAlignSearch(const AlignSearchArgs& a, hipStream_t stream) {
+    if (a.call.nSegments == 0)
+        return hipSuccess;
+    const size_t ldsBytes = static_cast<size_t>(a.call.rowStates) * kAlignLdsBytesPerState;
+    hipLaunchKernelGGL(dev::alignViterbiSearch, dim3(a.call.nSegments), dim3(kAlignThreads), ldsBytes, stream, a);
     return hipGetLastError();
 }
 

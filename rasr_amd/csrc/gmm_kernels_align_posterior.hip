@@ -26,7 +26,11 @@
 //   alignPosteriorItems<true>   the item pass again with the minimum and 1 / sum known: writes the compact list.
 // Every f32 / f64 add, subtract, multiply and divide is an _rn intrinsic (the unit is also built with
 // -ffp-contract=off); exp and log1p are the device library's f64 functions.  No atomics.
+// alignPosteriorSweepSearch (gmm_aligner_posteriors_search_*) is the sweep with the search flag on: the retry loop of
+// feed(vector) around forward and end, the n-best step of gmm_align_search.hh in the prune (its digit counters are
+// integer LDS atomics); the other four launches are shared, and alignPosteriorSweep's code does not change with it.
 #include "gmm_align.hh"
+#include "gmm_align_search.hh"
 
 #include <cfloat>
 #include <cmath>
@@ -79,9 +83,13 @@ __device__ __forceinline__ double close64(double mn, double sum) {
     return v < DBL_MAX ? v : DBL_MAX;
 }
 
-template <bool kWave>
+// kSearch: the forward part and the end run inside the retry loop of feed(vector), with the n-best step in the prune; a
+// pass overwrites the cells of the one before, and the backward sweep runs once, over the last pass's.  Without it the
+// function is the one pass at a.pruning
+template <bool kWave, bool kSearch>
 __device__ __forceinline__ void sweepSegment(const AlignPosteriorArgs& a, const uint32_t segment, double* rows64,
-                                             float* rows32, uint8_t* marks, float* redV, uint32_t* redQ) {
+                                             float* rows32, uint8_t* marks, float* redV, uint32_t* redQ,
+                                             const SearchContext& sc) {
     constexpr uint32_t T   = kWave ? 64u : kAlignThreads;
     const AlignSegment sg  = a.segments[segment];
     const uint32_t     tid = threadIdx.x, n = sg.nStates, gb = sg.stateBegin, R = a.rowStates;
@@ -89,127 +97,178 @@ __device__ __forceinline__ void sweepSegment(const AlignPosteriorArgs& a, const 
     double* const      fwPot = a.fwPot + sg.cellBegin;
     double* const      bwPot = a.bwPot + sg.cellBegin;
     uint8_t* const     mark  = a.mark + sg.cellBegin;
+    const uint32_t     last = (sg.nFrames & 1u) * R;
+    float              pruning = a.pruning, previous = FLT_MAX;  // previous: lane 0's
+    uint32_t           iterations = 0;
+    if constexpr (kSearch)
+        pruning = sc.search->minPruning;
 
-    for (uint32_t q = tid; q < n; q += T) {
-        rows32[q] = 0.0f;
-        rows64[q] = 0.0;
-        marks[q]  = q == sg.initial;
-    }
-    sync<kWave>();
-
-    // forward
-    uint32_t hypotheses = 0;
-    for (uint32_t t = 0; t < sg.nFrames; ++t) {
-        const uint32_t       from = (t & 1u) * R, to = ((t & 1u) ^ 1u) * R;
-        const float* const   prev = rows32 + from;
-        const double* const  prevPot = rows64 + from;
-        const uint8_t* const prevMark = marks + from;
-        float* const         cur = rows32 + to;
-        double* const        curPot = rows64 + to;
-        uint8_t* const       curMark = marks + to;
-        const float* const   column = a.scores + sg.frameBegin + t;
-        const size_t         row = static_cast<size_t>(t) * n;
-        float                mn = FLT_MAX;
+    for (;;) {  // the passes of the search; one without it
         for (uint32_t q = tid; q < n; q += T) {
-            const uint32_t j0 = a.inOffset[gb + q], j1 = a.inOffset[gb + q + 1];
-            bool           reached = false;
-            float          score = 0.0f;
-            double         potMin = DBL_MAX;
-            uint32_t       jMin = j1, nActive = 0;
-            for (uint32_t j = j0; j < j1; ++j) {
-                const uint32_t p = a.inSource[j];
-                const float    w = a.inWeight[j];
-                const float    e = column[static_cast<size_t>(a.inMixture[j]) * a.scoreStride];
-                if (prevMark[p]) {
-                    const float arcScore = __fadd_rn(w, e);
-                    const float cand     = __fadd_rn(prev[p], arcScore);
-                    score                = reached ? collect32(score, cand) : cand;
-                    reached              = true;
-                    ++nActive;
-                    const double s = extend64(prevPot[p], arcScore);
-                    if (s <= potMin) {
-                        potMin = s;
-                        jMin   = j;
-                    }
-                }
-            }
-            double sum = 0.0;
-            if (nActive > 1)
-                for (uint32_t j = j0; j < j1; ++j) {
-                    const uint32_t p = a.inSource[j];
-                    if (j != jMin && prevMark[p]) {
-                        const float arcScore =
-                                __fadd_rn(a.inWeight[j], column[static_cast<size_t>(a.inMixture[j]) * a.scoreStride]);
-                        sum = __dadd_rn(sum, exp(__dsub_rn(potMin, extend64(prevPot[p], arcScore))));
-                    }
-                }
-            const double pot = close64(potMin, sum);
-            cur[q]           = score;
-            curPot[q]        = pot;
-            curMark[q]       = reached;
-            fwPot[row + q]   = pot;
-            if (reached)
-                mn = minStep(mn, score);
-        }
-        for (uint32_t d = 32; d; d >>= 1)
-            mn = minStep(mn, __shfl_xor(mn, d));
-        if constexpr (!kWave) {
-            if (lane == 0)
-                redV[wave] = mn;
-            __syncthreads();
-            mn = FLT_MAX;
-            for (uint32_t w = 0; w < kWaves; ++w)
-                mn = minStep(mn, redV[w]);
-        }
-        const float threshold = __fadd_rn(mn, a.pruning);
-        for (uint32_t q = tid; q < n; q += T) {
-            bool keep = false;
-            if (curMark[q]) {
-                keep       = cur[q] <= threshold;
-                curMark[q] = keep;
-                hypotheses += keep;
-            }
-            mark[row + q] = keep;
+            rows32[q] = 0.0f;
+            rows64[q] = 0.0;
+            marks[q]  = q == sg.initial;
         }
         sync<kWave>();
-    }
 
-    for (uint32_t d = 32; d; d >>= 1)
-        hypotheses += __shfl_xor(hypotheses, d);
-    if constexpr (!kWave) {
-        if (lane == 0)
-            redQ[wave] = hypotheses;
-        __syncthreads();
-        hypotheses = 0;
-        for (uint32_t w = 0; w < kWaves; ++w)
-            hypotheses += redQ[w];
-    }
-
-    // end: alignmentScore() over the active final states in ascending order
-    const uint32_t last = (sg.nFrames & 1u) * R;
-    if (tid == 0) {
-        float    result = FLT_MAX;
-        uint32_t has = 0;
-        for (uint32_t q = 0; q < n; ++q)
-            if (marks[last + q]) {
-                const float fw = a.finalWeight[gb + q];
-                if (fw != INFINITY) {
-                    const float v = __fadd_rn(fw, rows32[last + q]);
-                    result        = result == FLT_MAX ? v : collect32(result, v);
-                    has           = 1;
+        // forward
+        uint32_t hypotheses = 0;
+        for (uint32_t t = 0; t < sg.nFrames; ++t) {
+            const uint32_t       from = (t & 1u) * R, to = ((t & 1u) ^ 1u) * R;
+            const float* const   prev = rows32 + from;
+            const double* const  prevPot = rows64 + from;
+            const uint8_t* const prevMark = marks + from;
+            float* const         cur = rows32 + to;
+            double* const        curPot = rows64 + to;
+            uint8_t* const       curMark = marks + to;
+            const float* const   column = a.scores + sg.frameBegin + t;
+            const size_t         row = static_cast<size_t>(t) * n;
+            float                mn = FLT_MAX;
+            uint32_t             nReached = 0;  // kSearch only
+            for (uint32_t q = tid; q < n; q += T) {
+                const uint32_t j0 = a.inOffset[gb + q], j1 = a.inOffset[gb + q + 1];
+                bool           reached = false;
+                float          score = 0.0f;
+                double         potMin = DBL_MAX;
+                uint32_t       jMin = j1, nActive = 0;
+                for (uint32_t j = j0; j < j1; ++j) {
+                    const uint32_t p = a.inSource[j];
+                    const float    w = a.inWeight[j];
+                    const float    e = column[static_cast<size_t>(a.inMixture[j]) * a.scoreStride];
+                    if (prevMark[p]) {
+                        const float arcScore = __fadd_rn(w, e);
+                        const float cand     = __fadd_rn(prev[p], arcScore);
+                        score                = reached ? collect32(score, cand) : cand;
+                        reached              = true;
+                        ++nActive;
+                        const double s = extend64(prevPot[p], arcScore);
+                        if (s <= potMin) {
+                            potMin = s;
+                            jMin   = j;
+                        }
+                    }
+                }
+                double sum = 0.0;
+                if (nActive > 1)
+                    for (uint32_t j = j0; j < j1; ++j) {
+                        const uint32_t p = a.inSource[j];
+                        if (j != jMin && prevMark[p]) {
+                            const float arcScore =
+                                    __fadd_rn(a.inWeight[j], column[static_cast<size_t>(a.inMixture[j]) * a.scoreStride]);
+                            sum = __dadd_rn(sum, exp(__dsub_rn(potMin, extend64(prevPot[p], arcScore))));
+                        }
+                    }
+                const double pot = close64(potMin, sum);
+                cur[q]           = score;
+                curPot[q]        = pot;
+                curMark[q]       = reached;
+                fwPot[row + q]   = pot;
+                if (reached)
+                    mn = minStep(mn, score);
+                if constexpr (kSearch)
+                    nReached += reached;
+            }
+            for (uint32_t d = 32; d; d >>= 1) {
+                mn = minStep(mn, __shfl_xor(mn, d));
+                if constexpr (kSearch)
+                    nReached += __shfl_xor(nReached, d);
+            }
+            if constexpr (!kWave) {
+                if (lane == 0) {
+                    redV[wave] = mn;
+                    if constexpr (kSearch)
+                        sc.lds->reached[wave] = nReached;
+                }
+                __syncthreads();
+                mn = FLT_MAX;
+                for (uint32_t w = 0; w < kWaves; ++w)
+                    mn = minStep(mn, redV[w]);
+                if constexpr (kSearch) {
+                    nReached = 0;
+                    for (uint32_t w = 0; w < kWaves; ++w)
+                        nReached += sc.lds->reached[w];
                 }
             }
-        if (!has)
-            result = FLT_MAX;
-        if (a.outScore)
-            a.outScore[segment] = result;
-        if (a.outHypotheses)
-            a.outHypotheses[segment] = hypotheses;
-        a.segHas[segment] = has;
-        redQ[kWaves]      = has;
+            const float threshold = __fadd_rn(mn, pruning);
+            if constexpr (kSearch) {
+                // uniform over the workgroup: every lane holds the same count
+                if (sc.search->nBest < nReached)
+                    nBestStep<kWave>(cur, curMark, n, sc.search->nBest, __fadd_rn(threshold, 1.0f), *sc.lds);
+            }
+            for (uint32_t q = tid; q < n; q += T) {
+                bool keep = false;
+                if (curMark[q]) {
+                    keep       = cur[q] <= threshold;
+                    curMark[q] = keep;
+                    hypotheses += keep;
+                }
+                mark[row + q] = keep;
+            }
+            sync<kWave>();
+        }
+
+        for (uint32_t d = 32; d; d >>= 1)
+            hypotheses += __shfl_xor(hypotheses, d);
+        if constexpr (!kWave) {
+            if (lane == 0)
+                redQ[wave] = hypotheses;
+            __syncthreads();
+            hypotheses = 0;
+            for (uint32_t w = 0; w < kWaves; ++w)
+                hypotheses += redQ[w];
+        }
+
+        // end: alignmentScore() over the active final states in ascending order; in a search lane 0 then decides whether
+        // the pass was the last, and only the last one's results are written
+        const float at = pruning;
+        if constexpr (kSearch)
+            ++iterations;
+        if (tid == 0) {
+            float    result = FLT_MAX;
+            uint32_t has = 0;
+            for (uint32_t q = 0; q < n; ++q)
+                if (marks[last + q]) {
+                    const float fw = a.finalWeight[gb + q];
+                    if (fw != INFINITY) {
+                        const float v = __fadd_rn(fw, rows32[last + q]);
+                        result        = result == FLT_MAX ? v : collect32(result, v);
+                        has           = 1;
+                    }
+                }
+            if (!has)
+                result = FLT_MAX;
+            bool stop = true;
+            if constexpr (kSearch) {
+                stop = searchStops(*sc.search, result, hypotheses, sg.nFrames, iterations, previous, pruning);
+                sc.lds->stop = stop;
+                if (stop) {
+                    if (sc.outThreshold)
+                        sc.outThreshold[segment] = at;
+                    if (sc.outIterations)
+                        sc.outIterations[segment] = iterations;
+                }
+            }
+            if (stop) {
+                if (a.outScore)
+                    a.outScore[segment] = result;
+                if (a.outHypotheses)
+                    a.outHypotheses[segment] = hypotheses;
+                a.segHas[segment] = has;
+            }
+            redQ[kWaves] = has;
+        }
+        // the marks of the scratch are read below by other lanes than wrote them
+        sync<kWave, true>();
+        if constexpr (kSearch) {
+            if (!sc.lds->stop) {
+                // lane 0's next threshold is one f32 product of values every lane holds
+                if (tid != 0)
+                    pruning = __fmul_rn(pruning, sc.search->factor);
+                continue;
+            }
+        }
+        break;
     }
-    // the marks of the scratch are read below by other lanes than wrote them
-    sync<kWave, true>();
     if (!redQ[kWaves]) {
         if (tid == 0) {
             a.segTotalInv[segment] = 0.0;
@@ -334,9 +393,36 @@ __global__ __launch_bounds__(kAlignThreads) void alignPosteriorSweep(AlignPoster
     const uint32_t      segment = a.order[blockIdx.x];
     if (a.segments[segment].nStates <= kAlignWaveStates) {
         if (threadIdx.x < 64)
-            sweepSegment<true>(a, segment, rows64, rows32, marks, redV, redQ);
+            sweepSegment<true, false>(a, segment, rows64, rows32, marks, redV, redQ, SearchContext{});
     } else {
-        sweepSegment<false>(a, segment, rows64, rows32, marks, redV, redQ);
+        sweepSegment<false, false>(a, segment, rows64, rows32, marks, redV, redQ, SearchContext{});
+    }
+}
+
+// the search call's sweep: the same workgroup per segment, each with its own number of forward passes
+__global__ __launch_bounds__(kAlignThreads) void alignPosteriorSweepSearch(AlignPosteriorSearchArgs sa) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    __shared__ float          redV[kWaves];
+    __shared__ uint32_t       redQ[kWaves + 1];
+    __shared__ SearchLds      searchLds;
+    static_assert(((GMM_ALIGN_MAX_STATES_POSTERIOR + 63u) & ~63u) * kAlignPosteriorLdsBytesPerState + sizeof(redV) +
+                                  sizeof(redQ) + sizeof(SearchLds) + 2 * kLdsAlign <= kLdsBytes,
+                  "the rows of the largest segment fit beside all static LDS of the search sweep");
+    const AlignPosteriorArgs& a = sa.call;
+    double* const             rows64 = reinterpret_cast<double*>(lds);
+    float* const              rows32 = reinterpret_cast<float*>(lds + 2u * a.rowStates * sizeof(double));
+    uint8_t* const            marks  = lds + 2u * a.rowStates * (sizeof(double) + sizeof(float));
+    const uint32_t            segment = a.order[blockIdx.x];
+    SearchContext             sc;
+    sc.search        = &sa.search;
+    sc.outThreshold  = sa.outThreshold;
+    sc.outIterations = sa.outIterations;
+    sc.lds           = &searchLds;
+    if (a.segments[segment].nStates <= kAlignWaveStates) {
+        if (threadIdx.x < 64)
+            sweepSegment<true, true>(a, segment, rows64, rows32, marks, redV, redQ, sc);
+    } else {
+        sweepSegment<false, true>(a, segment, rows64, rows32, marks, redV, redQ, sc);
     }
 }
 
@@ -524,12 +610,11 @@ __global__ __launch_bounds__(kAlignThreads) void alignPosteriorColumns(AlignPost
 
 }  // namespace dev
 
-hipError_t launchAlignPosteriors(const AlignPosteriorArgs& a, hipStream_t stream) {
-    if (a.nSegments == 0)
-        return hipSuccess;
-    const size_t   ldsBytes = static_cast<size_t>(a.rowStates) * kAlignPosteriorLdsBytesPerState;
+namespace {
+
+// the launches behind the sweep, the same for both calls
+hipError_t launchItems(const AlignPosteriorArgs& a, hipStream_t stream) {
     const uint32_t itemWaves = a.nFrames < kAlignItemWaves ? a.nFrames : kAlignItemWaves;
-    hipLaunchKernelGGL(dev::alignPosteriorSweep, dim3(a.nSegments), dim3(kAlignThreads), ldsBytes, stream, a);
     hipLaunchKernelGGL(dev::alignPosteriorItems<false>, dim3(itemWaves), dim3(64), 0, stream, a);
     hipLaunchKernelGGL(dev::alignPosteriorScan, dim3(1), dim3(kAlignThreads), 0, stream, a);
     if (a.outColumnOffset) {
@@ -539,6 +624,24 @@ hipError_t launchAlignPosteriors(const AlignPosteriorArgs& a, hipStream_t stream
     if (a.outItemFrame)
         hipLaunchKernelGGL(dev::alignPosteriorItems<true>, dim3(itemWaves), dim3(64), 0, stream, a);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launchAlignPosteriors(const AlignPosteriorArgs& a, hipStream_t stream) {
+    if (a.nSegments == 0)
+        return hipSuccess;
+    const size_t ldsBytes = static_cast<size_t>(a.rowStates) * kAlignPosteriorLdsBytesPerState;
+    hipLaunchKernelGGL(dev::alignPosteriorSweep, dim3(a.nSegments), dim3(kAlignThreads), ldsBytes, stream, a);
+    return launchItems(a, stream);
+}
+
+hipError_t launchAlignPosteriorsSearch(const AlignPosteriorSearchArgs& a, hipStream_t stream) {
+    if (a.call.nSegments == 0)
+        return hipSuccess;
+    const size_t ldsBytes = static_cast<size_t>(a.call.rowStates) * kAlignPosteriorLdsBytesPerState;
+    hipLaunchKernelGGL(dev::alignPosteriorSweepSearch, dim3(a.call.nSegments), dim3(kAlignThreads), ldsBytes, stream, a);
+    return launchItems(a.call, stream);
 }
 
 }  // namespace rasr_gmm
