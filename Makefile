@@ -42,7 +42,7 @@ ADAPT_HDRS = $(PAIR_HDRS) $(SRC)/gmm_adapt.hh
 # include/rasr_gmm_mllr.h: the units behind it depend on these besides HDRS
 MLLR_HDRS = $(PAIR_HDRS) $(SRC)/gmm_mllr.hh
 # include/rasr_gmm_align.h: the units behind it depend on these (the kernel unit on nothing else)
-ALIGN_HDRS = include/rasr_gmm_align.h include/rasr_gmm.h $(SRC)/gmm_align.hh $(SRC)/gmm_align_search.hh \
+ALIGN_HDRS = include/rasr_gmm_align.h include/rasr_gmm.h $(SRC)/gmm_align.hh $(SRC)/gmm_align_step.hh \
              $(SRC)/host/AlignGraph.hh
 DRIVER    = $(BUILD)/tests/feature_scorer_driver
 

@@ -170,38 +170,58 @@ class Aligner:
         segment without an alignment; columns of no segment keep what out_mixture / out_state / out_arc held, NONE in
         tensors allocated here, so the accumulate calls skip them),
         "score" [n_segments] float32 (FLT_MAX without an alignment) and "hypotheses" [n_segments] int32."""
-        if isinstance(scores, np.ndarray):
-            return self._align_host(scores, pruning_threshold, n_table_frames, out_mixture, out_state, out_arc, search)
-        import torch
-        if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1 or scores.shape[0] != self.n_mixtures:
-            raise ValueError("scores must be a float32 [n_mixtures, >= n_table_frames] tensor with unit column stride")
+        host = isinstance(scores, np.ndarray)
+        if host:
+            scores = np.ascontiguousarray(scores, dtype=np.float32)
+            if scores.ndim != 2 or scores.shape[0] != self.n_mixtures:
+                raise ValueError("scores must be [n_mixtures, >= n_table_frames]")
+            kind, ptr, stride, tail = "array", _ptr, scores.shape[1], ()
+
+            def new(n, t, fill=None):
+                return np.empty(n, dtype=t) if fill is None else np.full(n, fill, dtype=t)
+
+            def bad(t):
+                return not isinstance(t, np.ndarray) or t.size < f or t.itemsize != 4 or not t.flags.c_contiguous
+        else:
+            import torch
+            if (scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1
+                    or scores.shape[0] != self.n_mixtures):
+                raise ValueError("scores must be a float32 [n_mixtures, >= n_table_frames] tensor with unit column stride")
+            if stream is None:
+                stream = torch.cuda.current_stream(scores.device)
+            s = getattr(stream, "cuda_stream", stream)
+            kind, stride, tail = "tensor", int(scores.stride(0)), (ctypes.c_void_p(s) if s else None,)
+
+            def ptr(t):
+                return ctypes.c_void_p(t.data_ptr())
+
+            def new(n, t, fill=None):
+                t = getattr(torch, t)
+                return (torch.empty(n, dtype=t, device=scores.device) if fill is None
+                        else torch.full((n,), fill, dtype=t, device=scores.device))
+
+            def bad(t):
+                return t.numel() < f or t.element_size() != 4 or t.dtype.is_floating_point or not t.is_contiguous()
         f = int(scores.shape[1] if n_table_frames is None else n_table_frames)
-        cols = []
-        for name, t in (("out_mixture", out_mixture), ("out_state", out_state), ("out_arc", out_arc)):
+        out = {}
+        for k, t in (("mixture", out_mixture), ("state", out_state), ("arc", out_arc)):
             if t is None:
-                t = torch.full((f,), -1, dtype=torch.int32, device=scores.device)
-            elif t.numel() < f or t.element_size() != 4 or t.dtype.is_floating_point or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous int32 / uint32 tensor of n_table_frames entries")
-            cols.append(t)
-        score = torch.empty(self.n_segments, dtype=torch.float32, device=scores.device)
-        hyp = torch.empty(self.n_segments, dtype=torch.int32, device=scores.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(scores.device)
-        s = getattr(stream, "cuda_stream", stream)
-        out = {"mixture": cols[0], "state": cols[1], "arc": cols[2], "score": score, "hypotheses": hyp}
+                t = new(f, "int32", -1)
+            elif bad(t):
+                raise ValueError(f"out_{k} must be a contiguous int32 / uint32 {kind} of n_table_frames entries")
+            out[k] = t
+        shapes = (("score", "float32"), ("hypotheses", "int32"))
+        name = "gmm_aligner_align_"
         if search is not None:
-            out["threshold"] = torch.empty(self.n_segments, dtype=torch.float32, device=scores.device)
-            out["iterations"] = torch.empty(self.n_segments, dtype=torch.int32, device=scores.device)
-            rc = self._lib.gmm_aligner_align_search_device(
-                self._h, ctypes.c_void_p(scores.data_ptr()), f, int(scores.stride(0)), ctypes.byref(search._struct()),
-                *(ctypes.c_void_p(t.data_ptr()) for t in out.values()), ctypes.c_void_p(s) if s else None)
-            _capi.check(rc, "gmm_aligner_align_search_device")
-            return out
-        rc = self._lib.gmm_aligner_align_device(
-            self._h, ctypes.c_void_p(scores.data_ptr()), f, int(scores.stride(0)), float(pruning_threshold),
-            *(ctypes.c_void_p(t.data_ptr()) for t in cols), ctypes.c_void_p(score.data_ptr()),
-            ctypes.c_void_p(hyp.data_ptr()), ctypes.c_void_p(s) if s else None)
-        _capi.check(rc, "gmm_aligner_align_device")
+            shapes += (("threshold", "float32"), ("iterations", "int32"))
+            name += "search_"
+            pruning = ctypes.byref(search._struct())
+        else:
+            pruning = float(pruning_threshold)
+        out.update((k, new(self.n_segments, t)) for k, t in shapes)
+        name += "host" if host else "device"
+        rc = getattr(self._lib, name)(self._h, ptr(scores), f, stride, pruning, *(ptr(t) for t in out.values()), *tail)
+        _capi.check(rc, name)
         return out
 
     def posteriors(self, scores, pruning_threshold: float = float("inf"), min_posterior: float = 0.0, max_items=None,
@@ -276,31 +296,4 @@ class Aligner:
         for k in ("frame", "mixture", "weight"):
             out[k] = out[k][:n]
         out["n_items"] = n
-        return out
-
-    def _align_host(self, scores, pruning_threshold, n_table_frames, out_mixture, out_state, out_arc, search=None) -> dict:
-        scores = np.ascontiguousarray(scores, dtype=np.float32)
-        if scores.ndim != 2 or scores.shape[0] != self.n_mixtures:
-            raise ValueError("scores must be [n_mixtures, >= n_table_frames]")
-        f = int(scores.shape[1] if n_table_frames is None else n_table_frames)
-        cols = []
-        for name, t in (("out_mixture", out_mixture), ("out_state", out_state), ("out_arc", out_arc)):
-            if t is None:
-                t = np.full(f, -1, dtype=np.int32)
-            elif not isinstance(t, np.ndarray) or t.size < f or t.itemsize != 4 or not t.flags.c_contiguous:
-                raise ValueError(f"{name} must be a contiguous int32 / uint32 array of n_table_frames entries")
-            cols.append(t)
-        score = np.empty(self.n_segments, dtype=np.float32)
-        hyp = np.empty(self.n_segments, dtype=np.int32)
-        out = {"mixture": cols[0], "state": cols[1], "arc": cols[2], "score": score, "hypotheses": hyp}
-        if search is not None:
-            out["threshold"] = np.empty(self.n_segments, dtype=np.float32)
-            out["iterations"] = np.empty(self.n_segments, dtype=np.int32)
-            rc = self._lib.gmm_aligner_align_search_host(self._h, _ptr(scores), f, scores.shape[1],
-                                                         ctypes.byref(search._struct()), *map(_ptr, out.values()))
-            _capi.check(rc, "gmm_aligner_align_search_host")
-            return out
-        rc = self._lib.gmm_aligner_align_host(self._h, _ptr(scores), f, scores.shape[1], float(pruning_threshold),
-                                              *map(_ptr, cols), _ptr(score), _ptr(hyp))
-        _capi.check(rc, "gmm_aligner_align_host")
         return out

@@ -1,6 +1,7 @@
 // gmm_align.cc -- the handle behind include/rasr_gmm_align.h: its device memory (the batch's tables and the
 // backpointer scratch, all allocated at creation), set_segments (host/AlignGraph.cc validates and builds, this unit
-// uploads), the checks and the launch of an align call (gmm_kernels_align.hip), the host call's staging.
+// uploads), the checks and the launch of the calls of both modes (gmm_kernels_align.hip, gmm_kernels_align_posterior.hip)
+// and the host calls' staging.  A call travels as small structs: the table, the mode's outputs, the search part.
 #include <cfloat>
 #include <cmath>
 #include <memory>
@@ -72,32 +73,46 @@ hipError_t put(DeviceBuffer<T>& dst, const std::vector<T>& src) {
     return src.empty() ? hipSuccess : hipMemcpy(dst.get(), src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
-// the checks of both align calls; nothing is written or enqueued before they pass
-int checkAlignCall(const gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
-                   const void* outMixture, const void* outState, const void* outArc, const void* outScore,
-                   const void* outHypotheses) {
+// the outputs of a Viterbi call, device or host pointers as the call is; each may be NULL
+struct ViterbiOut {
+    uint32_t *mixture, *state, *arc;  // [table columns]
+    float*    score;                  // [nSegments]
+    uint32_t* hypotheses;             // [nSegments]
+};
+
+// what a Baum-Welch call adds to the table and the threshold: the item filter and capacity, and the outputs
+struct PosteriorOut {
+    float     minPosterior;
+    uint32_t  maxItems;
+    uint32_t *itemFrame, *itemMixture;
+    double*   itemWeight;
+    uint32_t *columnOffset, *nItems;
+    float*    score;
+    uint32_t* hypotheses;
+    double*   logTotal;
+};
+
+// the checks of all calls; nothing is written or enqueued before they pass
+int checkCall(const gmm_aligner* h, const AlignTable& t, bool anyOutput) {
     if (!h)
         return fail(GMM_ERR_INVALID_ARGUMENT, "null aligner");
-    if (!scores)
+    if (!t.scores)
         return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: null scores");
-    if (!outMixture && !outState && !outArc && !outScore && !outHypotheses)
+    if (!anyOutput)
         return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: no output requested");
     if (h->nSegments == 0)
         return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: no segments set");
-    if (scoreStride < nTableFrames)
+    if (t.scoreStride < t.nTableFrames)
         return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: score_stride below n_table_frames");
-    if (h->frameEnd > nTableFrames)
+    if (h->frameEnd > t.nTableFrames)
         return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: a segment ends at column " + std::to_string(h->frameEnd) +
-                                                      ", past n_table_frames " + std::to_string(nTableFrames));
+                                                      ", past n_table_frames " + std::to_string(t.nTableFrames));
     return GMM_OK;
 }
 
-// the search outputs of a search call; search == nullptr: the fixed-threshold call
-struct SearchCall {
-    const AlignSearch* search        = nullptr;
-    float*             outThreshold  = nullptr;
-    uint32_t*          outIterations = nullptr;
-};
+int checkModeCall(const gmm_aligner* h, const AlignTable& t, const ViterbiOut& o) {
+    return checkCall(h, t, o.mixture || o.state || o.arc || o.score || o.hypotheses);
+}
 
 // The checks of gmm_align_search, before anything is written; fills `out`.  The schedule is counted with the f32
 // multiply the kernels use.
@@ -136,36 +151,42 @@ int checkSearch(const gmm_align_search* s, AlignSearch& out) {
     return GMM_OK;
 }
 
-int alignOn(gmm_aligner* h, const float* scores, uint32_t scoreStride, float pruning, uint32_t* outMixture,
-            uint32_t* outState, uint32_t* outArc, float* outScore, uint32_t* outHypotheses, hipStream_t stream,
-            const SearchCall& sc = SearchCall{}) {
-    AlignArgs a{};
-    a.segments      = h->dSegments.get();
-    a.order         = h->dOrder.get();
-    a.inOffset      = h->dInOffset.get();
-    a.inSource      = h->dInSource.get();
-    a.inArc         = h->dInArc.get();
-    a.inMixture     = h->dInMixture.get();
-    a.inWeight      = h->dInWeight.get();
-    a.finalWeight   = h->dFinalWeight.get();
-    a.scores        = scores;
-    a.scoreStride   = scoreStride;
-    a.pruning       = pruning;
-    a.cells         = h->dCells.get();
-    a.outMixture    = outMixture;
-    a.outState      = outState;
-    a.outArc        = outArc;
-    a.outScore      = outScore;
-    a.outHypotheses = outHypotheses;
-    a.nSegments     = h->nSegments;
-    a.rowStates     = h->rowStates;
-    const hipError_t e = sc.search ? launchAlignSearch(AlignSearchArgs{a, *sc.search, sc.outThreshold, sc.outIterations}, stream)
-                                   : launchAlign(a, stream);
-    // what was enqueued uses the handle's tables and scratch
+// the batch part of both modes' arguments
+void fillBatch(const gmm_aligner* h, AlignBatch& b) {
+    b.segments    = h->dSegments.get();
+    b.order       = h->dOrder.get();
+    b.inOffset    = h->dInOffset.get();
+    b.inSource    = h->dInSource.get();
+    b.inArc       = h->dInArc.get();
+    b.inMixture   = h->dInMixture.get();
+    b.inWeight    = h->dInWeight.get();
+    b.finalWeight = h->dFinalWeight.get();
+    b.nSegments   = h->nSegments;
+    b.rowStates   = h->rowStates;
+}
+
+// what was enqueued uses the handle's tables and scratch: the event is recorded whether or not the launch failed
+int recordDone(gmm_aligner* h, hipError_t launched, hipStream_t stream) {
     GMM_HIP_CHECK(hipEventRecord(h->done.get(), stream));
     h->pending = true;
-    GMM_HIP_CHECK(e);
+    GMM_HIP_CHECK(launched);
     return GMM_OK;
+}
+
+int callOn(gmm_aligner* h, const AlignTable& table, float pruning, const ViterbiOut& o, const AlignSearchCall& search,
+            hipStream_t stream) {
+    AlignArgs a{};
+    fillBatch(h, a);
+    static_cast<AlignTable&>(a) = table;
+    a.search                    = search;
+    a.pruning                   = pruning;
+    a.cells                     = h->dCells.get();
+    a.outMixture                = o.mixture;
+    a.outState                  = o.state;
+    a.outArc                    = o.arc;
+    a.outScore                  = o.score;
+    a.outHypotheses             = o.hypotheses;
+    return recordDone(h, launchAlign(a, stream), stream);
 }
 
 // the ordered frames of a batch fit 32 bits (the frame ranges are disjoint columns of a table)
@@ -229,18 +250,14 @@ int preparePosterior(gmm_aligner* h) {
 }
 
 // the checks of both posterior calls; nothing is written or enqueued before they pass
-int checkPosteriorCall(const gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
-                       uint32_t maxItems, const void* itemFrame, const void* itemMixture, const void* itemWeight,
-                       const void* columnOffset, const void* nItems, const void* outScore, const void* outHypotheses,
-                       const void* logTotal) {
-    const bool items = itemFrame || itemMixture || itemWeight;
-    const int  rc = checkAlignCall(h, scores, nTableFrames, scoreStride, itemFrame, columnOffset, nItems,
-                                   outScore ? outScore : logTotal, outHypotheses);
+int checkModeCall(const gmm_aligner* h, const AlignTable& t, const PosteriorOut& o) {
+    const bool items = o.itemFrame || o.itemMixture || o.itemWeight;
+    const int  rc = checkCall(h, t, o.itemFrame || o.columnOffset || o.nItems || o.score || o.logTotal || o.hypotheses);
     if (rc != GMM_OK)
         return rc;
-    if (items && !(itemFrame && itemMixture && itemWeight))
+    if (items && !(o.itemFrame && o.itemMixture && o.itemWeight))
         return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: out_item_frame, out_item_mixture and out_item_weight go together");
-    if (items && maxItems == 0)
+    if (items && o.maxItems == 0)
         return fail(GMM_ERR_INVALID_ARGUMENT, "aligner: item arrays with max_items 0");
     if (h->maxSegmentStates > GMM_ALIGN_MAX_STATES_POSTERIOR)
         return fail(GMM_ERR_UNSUPPORTED, "aligner: a segment has " + std::to_string(h->maxSegmentStates) +
@@ -251,68 +268,206 @@ int checkPosteriorCall(const gmm_aligner* h, const float* scores, uint32_t nTabl
     return GMM_OK;
 }
 
-int posteriorsOn(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride, float pruning,
-                 float minPosterior, uint32_t maxItems, uint32_t* itemFrame, uint32_t* itemMixture, double* itemWeight,
-                 uint32_t* columnOffset, uint32_t* nItems, float* outScore, uint32_t* outHypotheses, double* logTotal,
-                 hipStream_t stream, const SearchCall& sc = SearchCall{}) {
+int callOn(gmm_aligner* h, const AlignTable& table, float pruning, const PosteriorOut& o, const AlignSearchCall& search,
+           hipStream_t stream) {
     const int rc = preparePosterior(h);
     if (rc != GMM_OK)
         return rc;
     AlignPosteriorArgs a{};
-    a.segments        = h->dSegments.get();
-    a.order           = h->dOrder.get();
-    a.inOffset        = h->dInOffset.get();
-    a.inSource        = h->dInSource.get();
-    a.inMixture       = h->dInMixture.get();
-    a.inWeight        = h->dInWeight.get();
-    a.finalWeight     = h->dFinalWeight.get();
-    a.arcOffset       = h->dArcOffset.get();
-    a.arcTarget       = h->dArcTarget.get();
-    a.arcMixture      = h->dArcMixture.get();
-    a.arcWeight       = h->dArcWeight.get();
-    a.groupOffset     = h->dGroupOffset.get();
-    a.groupMixture    = h->dGroupMixture.get();
-    a.groupArcOffset  = h->dGroupArcOffset.get();
-    a.groupSource     = h->dGroupSource.get();
-    a.groupTarget     = h->dGroupTarget.get();
-    a.groupWeight     = h->dGroupWeight.get();
-    a.colSegment      = h->dColSegment.get();
-    a.colFrameOffset  = h->dColFrameOffset.get();
-    a.scores          = scores;
-    a.scoreStride     = scoreStride;
-    a.nTableFrames    = nTableFrames;
-    a.pruning         = pruning;
-    a.minPosterior    = minPosterior;
-    a.maxItems        = maxItems;
-    a.fwPot           = h->dFwPot.get();
-    a.bwPot           = h->dBwPot.get();
-    a.mark            = h->dMark.get();
-    a.segTotalInv     = h->dSegTotalInv.get();
-    a.segHas          = h->dSegHas.get();
-    a.frameMin        = h->dFrameMin.get();
-    a.frameInv        = h->dFrameInv.get();
-    a.frameCount      = h->dFrameCount.get();
-    a.waveWeights     = h->dWaveWeights.get();
-    a.rowGroups       = h->rowGroups;
-    a.outItemFrame    = itemFrame;
-    a.outItemMixture  = itemMixture;
-    a.outItemWeight   = itemWeight;
-    a.outColumnOffset = columnOffset;
-    a.outNItems       = nItems;
-    a.outScore        = outScore;
-    a.outHypotheses   = outHypotheses;
-    a.outLogTotal     = logTotal;
-    a.nSegments       = h->nSegments;
-    a.rowStates       = h->rowStates;
-    a.nFrames         = static_cast<uint32_t>(h->posterior.nFrames);
-    const hipError_t e =
-            sc.search ? launchAlignPosteriorsSearch(AlignPosteriorSearchArgs{a, *sc.search, sc.outThreshold, sc.outIterations},
-                                                    stream)
-                      : launchAlignPosteriors(a, stream);
-    GMM_HIP_CHECK(hipEventRecord(h->done.get(), stream));
-    h->pending = true;
-    GMM_HIP_CHECK(e);
+    fillBatch(h, a);
+    static_cast<AlignTable&>(a) = table;
+    a.search                    = search;
+    a.arcOffset                 = h->dArcOffset.get();
+    a.arcTarget                 = h->dArcTarget.get();
+    a.arcMixture                = h->dArcMixture.get();
+    a.arcWeight                 = h->dArcWeight.get();
+    a.groupOffset               = h->dGroupOffset.get();
+    a.groupMixture              = h->dGroupMixture.get();
+    a.groupArcOffset            = h->dGroupArcOffset.get();
+    a.groupSource               = h->dGroupSource.get();
+    a.groupTarget               = h->dGroupTarget.get();
+    a.groupWeight               = h->dGroupWeight.get();
+    a.colSegment                = h->dColSegment.get();
+    a.colFrameOffset            = h->dColFrameOffset.get();
+    a.pruning                   = pruning;
+    a.minPosterior              = o.minPosterior;
+    a.maxItems                  = o.maxItems;
+    a.fwPot                     = h->dFwPot.get();
+    a.bwPot                     = h->dBwPot.get();
+    a.mark                      = h->dMark.get();
+    a.segTotalInv               = h->dSegTotalInv.get();
+    a.segHas                    = h->dSegHas.get();
+    a.frameMin                  = h->dFrameMin.get();
+    a.frameInv                  = h->dFrameInv.get();
+    a.frameCount                = h->dFrameCount.get();
+    a.waveWeights               = h->dWaveWeights.get();
+    a.rowGroups                 = h->rowGroups;
+    a.outItemFrame              = o.itemFrame;
+    a.outItemMixture            = o.itemMixture;
+    a.outItemWeight             = o.itemWeight;
+    a.outColumnOffset           = o.columnOffset;
+    a.outNItems                 = o.nItems;
+    a.outScore                  = o.score;
+    a.outHypotheses             = o.hypotheses;
+    a.outLogTotal               = o.logTotal;
+    a.nFrames                   = static_cast<uint32_t>(h->posterior.nFrames);
+    return recordDone(h, launchAlignPosteriors(a, stream), stream);
+}
+
+// An optional output of a host call, staged on the device: room for it if the host pointer is set, the device pointer or
+// NULL for the launch, the copy back of its first elements
+template <class T>
+struct Staged {
+    T*              host = nullptr;
+    size_t          size = 0;
+    DeviceBuffer<T> dev;
+
+    hipError_t alloc(T* hostPointer, size_t n) {
+        host = hostPointer;
+        size = n;
+        return host ? dev.alloc(n) : hipSuccess;
+    }
+    T*         get() const { return host ? dev.get() : nullptr; }
+    hipError_t send() const {
+        return host && size ? hipMemcpy(dev.get(), host, size * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+    }
+    hipError_t fetch(size_t n) const {
+        return host && n ? hipMemcpy(host, dev.get(), n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
+    }
+    hipError_t fetch() const { return fetch(size); }
+};
+
+// The staging that both host calls share: the device is set and the last call's kernels are done before anything is
+// staged; the table, dense; the per-segment outputs of both modes and of the search
+struct HostCall {
+    DeviceBuffer<float> dTable;
+    Staged<float>       score, threshold;
+    Staged<uint32_t>    hypotheses, iterations;
+    AlignTable          table{};   // the staged table
+    AlignSearchCall     search{};  // the search with the staged outputs
+
+    int begin(gmm_aligner* h, const AlignTable& t, float* outScore, uint32_t* outHypotheses, const AlignSearchCall& hs) {
+        GMM_HIP_CHECK(hipSetDevice(h->device));
+        const int rc = waitDone(h);
+        if (rc != GMM_OK)
+            return rc;
+        const size_t F = t.nTableFrames, M = h->cap.nMixtures, S = h->nSegments;
+        GMM_HIP_CHECK(dTable.alloc(M * F));
+        GMM_HIP_CHECK(score.alloc(outScore, S));
+        GMM_HIP_CHECK(hypotheses.alloc(outHypotheses, S));
+        GMM_HIP_CHECK(threshold.alloc(hs.outThreshold, S));
+        GMM_HIP_CHECK(iterations.alloc(hs.outIterations, S));
+        if (F)
+            GMM_HIP_CHECK(hipMemcpy2D(dTable.get(), F * sizeof(float), t.scores,
+                                      static_cast<size_t>(t.scoreStride) * sizeof(float), F * sizeof(float), M,
+                                      hipMemcpyHostToDevice));
+        table                = AlignTable{dTable.get(), t.nTableFrames, t.nTableFrames};
+        search               = hs;
+        search.outThreshold  = threshold.get();
+        search.outIterations = iterations.get();
+        return GMM_OK;
+    }
+    // the copies on the default stream wait for the kernels and are synchronous
+    int fetch() const {
+        GMM_HIP_CHECK(score.fetch());
+        GMM_HIP_CHECK(hypotheses.fetch());
+        GMM_HIP_CHECK(threshold.fetch());
+        GMM_HIP_CHECK(iterations.fetch());
+        return GMM_OK;
+    }
+};
+
+// both host align calls, behind their checks; hs: the search with its HOST outputs
+int callHost(gmm_aligner* h, const AlignTable& table, float pruning, const ViterbiOut& o, const AlignSearchCall& hs) {
+    HostCall call;
+    int      rc = call.begin(h, table, o.score, o.hypotheses, hs);
+    if (rc != GMM_OK)
+        return rc;
+    // the per-column outputs start from the host arrays, whose columns of no segment are kept
+    Staged<uint32_t> columns[3];
+    uint32_t* const  host[3] = {o.mixture, o.state, o.arc};
+    for (int c = 0; c < 3; ++c) {
+        GMM_HIP_CHECK(columns[c].alloc(host[c], table.nTableFrames));
+        GMM_HIP_CHECK(columns[c].send());
+    }
+    const ViterbiOut staged{columns[0].get(), columns[1].get(), columns[2].get(), call.score.get(),
+                            call.hypotheses.get()};
+    rc = callOn(h, call.table, pruning, staged, call.search, nullptr);
+    if (rc != GMM_OK) {
+        (void)hipStreamSynchronize(nullptr);  // the buffers go with this scope
+        return rc;
+    }
+    for (const Staged<uint32_t>& c : columns)
+        GMM_HIP_CHECK(c.fetch());
+    if ((rc = call.fetch()) != GMM_OK)
+        return rc;
+    GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
     return GMM_OK;
+}
+
+// both host posterior calls, behind their checks; hs: the search with its HOST outputs
+int callHost(gmm_aligner* h, const AlignTable& table, float pruning, const PosteriorOut& o, const AlignSearchCall& hs) {
+    HostCall call;
+    int      rc = call.begin(h, table, o.score, o.hypotheses, hs);
+    if (rc != GMM_OK)
+        return rc;
+    const size_t           I = o.itemFrame ? o.maxItems : 0;
+    Staged<uint32_t>       itemFrame, itemMixture, columnOffset;
+    Staged<double>         itemWeight, logTotal;
+    DeviceBuffer<uint32_t> dCount;  // read back whether or not the caller asks for it
+    GMM_HIP_CHECK(itemFrame.alloc(o.itemFrame, I));
+    GMM_HIP_CHECK(itemMixture.alloc(o.itemMixture, I));
+    GMM_HIP_CHECK(itemWeight.alloc(o.itemWeight, I));
+    GMM_HIP_CHECK(columnOffset.alloc(o.columnOffset, static_cast<size_t>(table.nTableFrames) + 1));
+    GMM_HIP_CHECK(logTotal.alloc(o.logTotal, h->nSegments));
+    GMM_HIP_CHECK(dCount.alloc(1));
+    const PosteriorOut staged{o.minPosterior,   o.maxItems,         itemFrame.get(), itemMixture.get(),
+                              itemWeight.get(), columnOffset.get(), dCount.get(),    call.score.get(),
+                              call.hypotheses.get(), logTotal.get()};
+    rc = callOn(h, call.table, pruning, staged, call.search, nullptr);
+    if (rc != GMM_OK) {
+        (void)hipStreamSynchronize(nullptr);  // the buffers go with this scope
+        return rc;
+    }
+    uint32_t count = 0;
+    GMM_HIP_CHECK(hipMemcpy(&count, dCount.get(), sizeof(count), hipMemcpyDeviceToHost));
+    if (o.nItems)
+        *o.nItems = count;
+    if ((rc = call.fetch()) != GMM_OK)
+        return rc;
+    GMM_HIP_CHECK(logTotal.fetch());
+    if (I && count > o.maxItems) {
+        GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
+        return fail(GMM_ERR_CAPACITY, "aligner: the call produces " + std::to_string(count) + " items, more than max_items " +
+                                              std::to_string(o.maxItems));
+    }
+    GMM_HIP_CHECK(itemFrame.fetch(count));
+    GMM_HIP_CHECK(itemMixture.fetch(count));
+    GMM_HIP_CHECK(itemWeight.fetch(count));
+    GMM_HIP_CHECK(columnOffset.fetch());
+    GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
+    return GMM_OK;
+}
+
+// the search part of a search call before its checks: on, with the call's two outputs; `rule` is checkSearch's to fill
+AlignSearchCall searchOn(float* outThreshold, uint32_t* outIterations) {
+    return AlignSearchCall{AlignSearch{}, outThreshold, outIterations, 1};
+}
+
+// A call of either mode behind its entry point: the mode's checks and, in a search call (sc.on), the search's on the
+// caller's `rule`; then the launch on *stream on the handle's device or, without a stream, the host path
+template <class Out>
+int runCall(gmm_aligner* h, const AlignTable& table, float pruning, const Out& out, const gmm_align_search* rule,
+            AlignSearchCall sc, const hipStream_t* stream) {
+    int rc = checkModeCall(h, table, out);
+    if (rc == GMM_OK && sc.on)
+        rc = checkSearch(rule, sc.rule);
+    if (rc != GMM_OK)
+        return rc;
+    if (!stream)
+        return callHost(h, table, pruning, out, sc);
+    GMM_HIP_CHECK(hipSetDevice(h->device));
+    return callOn(h, table, pruning, out, sc, *stream);
 }
 
 }  // namespace
@@ -387,82 +542,24 @@ int gmm_aligner_set_segments(gmm_aligner* h, const gmm_align_graphs* graphs) {
     return GMM_OK;
 }
 
+// The calls: each builds the structs of the call for runCall.  A search call has no threshold of its
+// own: the kernels ignore `pruning`
+
 int gmm_aligner_align_device(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
                              float pruning, uint32_t* outMixture, uint32_t* outState, uint32_t* outArc, float* outScore,
                              uint32_t* outHypotheses, void* stream) {
-    const int rc = checkAlignCall(h, scores, nTableFrames, scoreStride, outMixture, outState, outArc, outScore, outHypotheses);
-    if (rc != GMM_OK)
-        return rc;
-    GMM_HIP_CHECK(hipSetDevice(h->device));
-    return alignOn(h, scores, scoreStride, pruning, outMixture, outState, outArc, outScore, outHypotheses,
-                   static_cast<hipStream_t>(stream));
-}
-
-// the staging of both host align calls, behind their checks; hs: the search with its HOST outputs
-static int alignHost(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride, float pruning,
-                     uint32_t* outMixture, uint32_t* outState, uint32_t* outArc, float* outScore, uint32_t* outHypotheses,
-                     const SearchCall& hs) {
-    int rc;
-    GMM_HIP_CHECK(hipSetDevice(h->device));
-    if ((rc = waitDone(h)) != GMM_OK)
-        return rc;
-    // the table, dense; the per-column outputs start from the host arrays, whose columns of no segment are kept
-    const size_t           F = nTableFrames, M = h->cap.nMixtures, S = h->nSegments;
-    DeviceBuffer<float>    dTable, dScore, dThreshold;
-    DeviceBuffer<uint32_t> dColumns, dHypotheses, dIterations;  // dColumns: mixture, state, arc
-    uint32_t* const        host[3] = {outMixture, outState, outArc};
-    uint32_t*              dev[3]  = {nullptr, nullptr, nullptr};
-    GMM_HIP_CHECK(dTable.alloc(M * F));
-    GMM_HIP_CHECK(dColumns.alloc(3 * F));
-    GMM_HIP_CHECK(dScore.alloc(S));
-    GMM_HIP_CHECK(dHypotheses.alloc(S));
-    SearchCall sc = hs;
-    if (hs.outThreshold) {
-        GMM_HIP_CHECK(dThreshold.alloc(S));
-        sc.outThreshold = dThreshold.get();
-    }
-    if (hs.outIterations) {
-        GMM_HIP_CHECK(dIterations.alloc(S));
-        sc.outIterations = dIterations.get();
-    }
-    if (F)
-        GMM_HIP_CHECK(hipMemcpy2D(dTable.get(), F * sizeof(float), scores, static_cast<size_t>(scoreStride) * sizeof(float),
-                                  F * sizeof(float), M, hipMemcpyHostToDevice));
-    for (int o = 0; o < 3; ++o)
-        if (host[o]) {
-            dev[o] = dColumns.get() + o * F;
-            GMM_HIP_CHECK(hipMemcpy(dev[o], host[o], F * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
-    rc = alignOn(h, dTable.get(), nTableFrames, pruning, dev[0], dev[1], dev[2], outScore ? dScore.get() : nullptr,
-                 outHypotheses ? dHypotheses.get() : nullptr, nullptr, sc);
-    if (rc != GMM_OK) {
-        (void)hipStreamSynchronize(nullptr);  // the buffers go with this scope
-        return rc;
-    }
-    // the copies on the default stream wait for the kernel and are synchronous
-    for (int o = 0; o < 3; ++o)
-        if (host[o])
-            GMM_HIP_CHECK(hipMemcpy(host[o], dev[o], F * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (outScore)
-        GMM_HIP_CHECK(hipMemcpy(outScore, dScore.get(), S * sizeof(float), hipMemcpyDeviceToHost));
-    if (outHypotheses)
-        GMM_HIP_CHECK(hipMemcpy(outHypotheses, dHypotheses.get(), S * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (hs.outThreshold)
-        GMM_HIP_CHECK(hipMemcpy(hs.outThreshold, dThreshold.get(), S * sizeof(float), hipMemcpyDeviceToHost));
-    if (hs.outIterations)
-        GMM_HIP_CHECK(hipMemcpy(hs.outIterations, dIterations.get(), S * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
-    return GMM_OK;
+    const hipStream_t on = static_cast<hipStream_t>(stream);
+    return runCall<ViterbiOut>(h, {scores, scoreStride, nTableFrames}, pruning,
+                               {outMixture, outState, outArc, outScore, outHypotheses}, nullptr,
+                               AlignSearchCall{}, &on);
 }
 
 int gmm_aligner_align_host(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride, float pruning,
                            uint32_t* outMixture, uint32_t* outState, uint32_t* outArc, float* outScore,
                            uint32_t* outHypotheses) {
-    const int rc = checkAlignCall(h, scores, nTableFrames, scoreStride, outMixture, outState, outArc, outScore, outHypotheses);
-    if (rc != GMM_OK)
-        return rc;
-    return alignHost(h, scores, nTableFrames, scoreStride, pruning, outMixture, outState, outArc, outScore, outHypotheses,
-                     SearchCall{});
+    return runCall<ViterbiOut>(h, {scores, scoreStride, nTableFrames}, pruning,
+                               {outMixture, outState, outArc, outScore, outHypotheses}, nullptr,
+                               AlignSearchCall{}, nullptr);
 }
 
 void gmm_default_align_search(gmm_align_search* s) {
@@ -480,126 +577,40 @@ int gmm_aligner_align_search_device(gmm_aligner* h, const float* scores, uint32_
                                     const gmm_align_search* search, uint32_t* outMixture, uint32_t* outState,
                                     uint32_t* outArc, float* outScore, uint32_t* outHypotheses, float* outThreshold,
                                     uint32_t* outIterations, void* stream) {
-    int rc = checkAlignCall(h, scores, nTableFrames, scoreStride, outMixture, outState, outArc, outScore, outHypotheses);
-    if (rc != GMM_OK)
-        return rc;
-    AlignSearch as{};
-    if ((rc = checkSearch(search, as)) != GMM_OK)
-        return rc;
-    GMM_HIP_CHECK(hipSetDevice(h->device));
-    return alignOn(h, scores, scoreStride, 0.0f, outMixture, outState, outArc, outScore, outHypotheses,
-                   static_cast<hipStream_t>(stream), SearchCall{&as, outThreshold, outIterations});
+    const hipStream_t on = static_cast<hipStream_t>(stream);
+    return runCall<ViterbiOut>(h, {scores, scoreStride, nTableFrames}, 0.0f,
+                               {outMixture, outState, outArc, outScore, outHypotheses}, search,
+                               searchOn(outThreshold, outIterations), &on);
 }
 
 int gmm_aligner_align_search_host(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
                                   const gmm_align_search* search, uint32_t* outMixture, uint32_t* outState,
                                   uint32_t* outArc, float* outScore, uint32_t* outHypotheses, float* outThreshold,
                                   uint32_t* outIterations) {
-    int rc = checkAlignCall(h, scores, nTableFrames, scoreStride, outMixture, outState, outArc, outScore, outHypotheses);
-    if (rc != GMM_OK)
-        return rc;
-    AlignSearch as{};
-    if ((rc = checkSearch(search, as)) != GMM_OK)
-        return rc;
-    return alignHost(h, scores, nTableFrames, scoreStride, 0.0f, outMixture, outState, outArc, outScore, outHypotheses,
-                     SearchCall{&as, outThreshold, outIterations});
+    return runCall<ViterbiOut>(h, {scores, scoreStride, nTableFrames}, 0.0f,
+                               {outMixture, outState, outArc, outScore, outHypotheses}, search,
+                               searchOn(outThreshold, outIterations), nullptr);
 }
 
 int gmm_aligner_posteriors_device(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
                                   float pruning, float minPosterior, uint32_t maxItems, uint32_t* itemFrame,
                                   uint32_t* itemMixture, double* itemWeight, uint32_t* columnOffset, uint32_t* nItems,
                                   float* outScore, uint32_t* outHypotheses, double* logTotal, void* stream) {
-    const int rc = checkPosteriorCall(h, scores, nTableFrames, scoreStride, maxItems, itemFrame, itemMixture, itemWeight,
-                                      columnOffset, nItems, outScore, outHypotheses, logTotal);
-    if (rc != GMM_OK)
-        return rc;
-    GMM_HIP_CHECK(hipSetDevice(h->device));
-    return posteriorsOn(h, scores, nTableFrames, scoreStride, pruning, minPosterior, maxItems, itemFrame, itemMixture,
-                        itemWeight, columnOffset, nItems, outScore, outHypotheses, logTotal,
-                        static_cast<hipStream_t>(stream));
-}
-
-// the staging of both host posterior calls, behind their checks; hs: the search with its HOST outputs
-static int posteriorsHost(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride, float pruning,
-                          float minPosterior, uint32_t maxItems, uint32_t* itemFrame, uint32_t* itemMixture,
-                          double* itemWeight, uint32_t* columnOffset, uint32_t* nItems, float* outScore,
-                          uint32_t* outHypotheses, double* logTotal, const SearchCall& hs) {
-    int rc;
-    GMM_HIP_CHECK(hipSetDevice(h->device));
-    if ((rc = waitDone(h)) != GMM_OK)
-        return rc;
-    const size_t           F = nTableFrames, M = h->cap.nMixtures, S = h->nSegments, I = itemFrame ? maxItems : 0;
-    DeviceBuffer<float>    dTable, dScore, dThreshold;
-    DeviceBuffer<uint32_t> dItems, dColumnOffset, dCount, dHypotheses, dIterations;  // dItems: frame, mixture
-    DeviceBuffer<double>   dWeight, dLogTotal;
-    SearchCall             sc = hs;
-    if (hs.outThreshold) {
-        GMM_HIP_CHECK(dThreshold.alloc(S));
-        sc.outThreshold = dThreshold.get();
-    }
-    if (hs.outIterations) {
-        GMM_HIP_CHECK(dIterations.alloc(S));
-        sc.outIterations = dIterations.get();
-    }
-    GMM_HIP_CHECK(dTable.alloc(M * F));
-    GMM_HIP_CHECK(dItems.alloc(2 * I));
-    GMM_HIP_CHECK(dWeight.alloc(I));
-    GMM_HIP_CHECK(dColumnOffset.alloc(F + 1));
-    GMM_HIP_CHECK(dCount.alloc(1));
-    GMM_HIP_CHECK(dScore.alloc(S));
-    GMM_HIP_CHECK(dHypotheses.alloc(S));
-    GMM_HIP_CHECK(dLogTotal.alloc(S));
-    if (F)
-        GMM_HIP_CHECK(hipMemcpy2D(dTable.get(), F * sizeof(float), scores, static_cast<size_t>(scoreStride) * sizeof(float),
-                                  F * sizeof(float), M, hipMemcpyHostToDevice));
-    rc = posteriorsOn(h, dTable.get(), nTableFrames, nTableFrames, pruning, minPosterior, maxItems,
-                      I ? dItems.get() : nullptr, I ? dItems.get() + I : nullptr, I ? dWeight.get() : nullptr,
-                      columnOffset ? dColumnOffset.get() : nullptr, dCount.get(), outScore ? dScore.get() : nullptr,
-                      outHypotheses ? dHypotheses.get() : nullptr, logTotal ? dLogTotal.get() : nullptr, nullptr, sc);
-    if (rc != GMM_OK) {
-        (void)hipStreamSynchronize(nullptr);  // the buffers go with this scope
-        return rc;
-    }
-    uint32_t count = 0;
-    GMM_HIP_CHECK(hipMemcpy(&count, dCount.get(), sizeof(count), hipMemcpyDeviceToHost));
-    if (nItems)
-        *nItems = count;
-    if (outScore)
-        GMM_HIP_CHECK(hipMemcpy(outScore, dScore.get(), S * sizeof(float), hipMemcpyDeviceToHost));
-    if (outHypotheses)
-        GMM_HIP_CHECK(hipMemcpy(outHypotheses, dHypotheses.get(), S * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (logTotal)
-        GMM_HIP_CHECK(hipMemcpy(logTotal, dLogTotal.get(), S * sizeof(double), hipMemcpyDeviceToHost));
-    if (hs.outThreshold)
-        GMM_HIP_CHECK(hipMemcpy(hs.outThreshold, dThreshold.get(), S * sizeof(float), hipMemcpyDeviceToHost));
-    if (hs.outIterations)
-        GMM_HIP_CHECK(hipMemcpy(hs.outIterations, dIterations.get(), S * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (I && count > maxItems) {
-        GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
-        return fail(GMM_ERR_CAPACITY, "aligner: the call produces " + std::to_string(count) + " items, more than max_items " +
-                                              std::to_string(maxItems));
-    }
-    if (I && count) {
-        GMM_HIP_CHECK(hipMemcpy(itemFrame, dItems.get(), count * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        GMM_HIP_CHECK(hipMemcpy(itemMixture, dItems.get() + I, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        GMM_HIP_CHECK(hipMemcpy(itemWeight, dWeight.get(), count * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    if (columnOffset)
-        GMM_HIP_CHECK(hipMemcpy(columnOffset, dColumnOffset.get(), (F + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    GMM_HIP_CHECK(hipStreamSynchronize(nullptr));
-    return GMM_OK;
+    const hipStream_t on = static_cast<hipStream_t>(stream);
+    return runCall<PosteriorOut>(h, {scores, scoreStride, nTableFrames}, pruning,
+                                 {minPosterior, maxItems, itemFrame, itemMixture, itemWeight, columnOffset, nItems,
+                                  outScore, outHypotheses, logTotal},
+                                 nullptr, AlignSearchCall{}, &on);
 }
 
 int gmm_aligner_posteriors_host(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
                                 float pruning, float minPosterior, uint32_t maxItems, uint32_t* itemFrame,
                                 uint32_t* itemMixture, double* itemWeight, uint32_t* columnOffset, uint32_t* nItems,
                                 float* outScore, uint32_t* outHypotheses, double* logTotal) {
-    const int rc = checkPosteriorCall(h, scores, nTableFrames, scoreStride, maxItems, itemFrame, itemMixture, itemWeight,
-                                      columnOffset, nItems, outScore, outHypotheses, logTotal);
-    if (rc != GMM_OK)
-        return rc;
-    return posteriorsHost(h, scores, nTableFrames, scoreStride, pruning, minPosterior, maxItems, itemFrame, itemMixture,
-                          itemWeight, columnOffset, nItems, outScore, outHypotheses, logTotal, SearchCall{});
+    return runCall<PosteriorOut>(h, {scores, scoreStride, nTableFrames}, pruning,
+                                 {minPosterior, maxItems, itemFrame, itemMixture, itemWeight, columnOffset, nItems,
+                                  outScore, outHypotheses, logTotal},
+                                 nullptr, AlignSearchCall{}, nullptr);
 }
 
 int gmm_aligner_posteriors_search_device(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
@@ -607,17 +618,11 @@ int gmm_aligner_posteriors_search_device(gmm_aligner* h, const float* scores, ui
                                          uint32_t* itemFrame, uint32_t* itemMixture, double* itemWeight,
                                          uint32_t* columnOffset, uint32_t* nItems, float* outScore, uint32_t* outHypotheses,
                                          double* logTotal, float* outThreshold, uint32_t* outIterations, void* stream) {
-    int rc = checkPosteriorCall(h, scores, nTableFrames, scoreStride, maxItems, itemFrame, itemMixture, itemWeight,
-                                columnOffset, nItems, outScore, outHypotheses, logTotal);
-    if (rc != GMM_OK)
-        return rc;
-    AlignSearch as{};
-    if ((rc = checkSearch(search, as)) != GMM_OK)
-        return rc;
-    GMM_HIP_CHECK(hipSetDevice(h->device));
-    return posteriorsOn(h, scores, nTableFrames, scoreStride, 0.0f, minPosterior, maxItems, itemFrame, itemMixture,
-                        itemWeight, columnOffset, nItems, outScore, outHypotheses, logTotal,
-                        static_cast<hipStream_t>(stream), SearchCall{&as, outThreshold, outIterations});
+    const hipStream_t on = static_cast<hipStream_t>(stream);
+    return runCall<PosteriorOut>(h, {scores, scoreStride, nTableFrames}, 0.0f,
+                                 {minPosterior, maxItems, itemFrame, itemMixture, itemWeight, columnOffset, nItems,
+                                  outScore, outHypotheses, logTotal},
+                                 search, searchOn(outThreshold, outIterations), &on);
 }
 
 int gmm_aligner_posteriors_search_host(gmm_aligner* h, const float* scores, uint32_t nTableFrames, uint32_t scoreStride,
@@ -625,16 +630,10 @@ int gmm_aligner_posteriors_search_host(gmm_aligner* h, const float* scores, uint
                                        uint32_t* itemFrame, uint32_t* itemMixture, double* itemWeight,
                                        uint32_t* columnOffset, uint32_t* nItems, float* outScore, uint32_t* outHypotheses,
                                        double* logTotal, float* outThreshold, uint32_t* outIterations) {
-    int rc = checkPosteriorCall(h, scores, nTableFrames, scoreStride, maxItems, itemFrame, itemMixture, itemWeight,
-                                columnOffset, nItems, outScore, outHypotheses, logTotal);
-    if (rc != GMM_OK)
-        return rc;
-    AlignSearch as{};
-    if ((rc = checkSearch(search, as)) != GMM_OK)
-        return rc;
-    return posteriorsHost(h, scores, nTableFrames, scoreStride, 0.0f, minPosterior, maxItems, itemFrame, itemMixture,
-                          itemWeight, columnOffset, nItems, outScore, outHypotheses, logTotal,
-                          SearchCall{&as, outThreshold, outIterations});
+    return runCall<PosteriorOut>(h, {scores, scoreStride, nTableFrames}, 0.0f,
+                                 {minPosterior, maxItems, itemFrame, itemMixture, itemWeight, columnOffset, nItems,
+                                  outScore, outHypotheses, logTotal},
+                                 search, searchOn(outThreshold, outIterations), nullptr);
 }
 
 }  // extern "C"

@@ -1,4 +1,6 @@
-// gmm_align.hh -- what gmm_align.cc (the handle behind include/rasr_gmm_align.h) and gmm_kernels_align.hip share.
+// gmm_align.hh -- what gmm_align.cc (the handle behind include/rasr_gmm_align.h) and the two kernel units
+// (gmm_kernels_align.hip, gmm_kernels_align_posterior.hip) share: the constants and the argument structs.  Both modes'
+// arguments are the batch, the table and the search part below plus what the mode adds.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -20,43 +22,50 @@ static_assert(GMM_ALIGN_MAX_STATES * kAlignLdsBytesPerState <= 60 * 1024, "the r
 static_assert(GMM_ALIGN_MAX_STATES <= 0x10000 && GMM_ALIGN_MAX_IN_ARCS <= 0xffff,
               "a backpointer packs (ordinal in the incoming list, source state) into 16 + 16 bits");
 
-struct AlignArgs {
-    // the batch (AlignPlan, uploaded by gmm_aligner_set_segments)
+// the batch (AlignPlan, uploaded by gmm_aligner_set_segments)
+struct AlignBatch {
     const AlignSegment* segments;
     const uint32_t*     order;  // workgroup b aligns segment order[b]
     const uint32_t *    inOffset, *inSource, *inArc, *inMixture;
     const float *       inWeight, *finalWeight;
-    // the call
-    const float* scores;  // [nMixtures][scoreStride]
-    uint32_t     scoreStride;
-    float        pruning;
-    uint32_t*    cells;   // the backpointers: (ordinal << 16) | source state per (frame, state) cell
-    uint32_t *   outMixture, *outState, *outArc;  // [table columns] or NULL
-    float*       outScore;                        // [nSegments] or NULL
-    uint32_t*    outHypotheses;                   // [nSegments] or NULL
-    uint32_t     nSegments;
-    uint32_t     rowStates;  // the LDS rows' length: the largest segment's states, rounded up to 64
+    uint32_t            nSegments;
+    uint32_t            rowStates;  // the LDS rows' length: the largest segment's states, rounded up to 64
 };
 
-hipError_t launchAlign(const AlignArgs& a, hipStream_t stream);
+// the score table of a call
+struct AlignTable {
+    const float* scores;  // [nMixtures][scoreStride]
+    uint32_t     scoreStride, nTableFrames;
+};
 
-// The search calls (gmm_aligner_*_search_*): gmm_align_search as the kernels read it, and the two outputs it adds.  The
-// kernels of the fixed-threshold calls keep their argument structs; the search kernels take them wrapped, and ignore
-// their `pruning`
+// gmm_align_search as the kernels read it
 struct AlignSearch {
     float    minPruning, maxPruning, factor;
     double   minAverage;
     uint32_t untilNoDifference, nBest;
 };
 
-struct AlignSearchArgs {
-    AlignArgs   call;
-    AlignSearch search;
+// The search part of a call (gmm_aligner_*_search_*): off in the fixed-threshold calls, whose kernels read none of it.
+// With it on the kernels ignore the call's `pruning`
+struct AlignSearchCall {
+    AlignSearch rule;
     float*      outThreshold;   // [nSegments] or NULL
     uint32_t*   outIterations;  // [nSegments] or NULL
+    uint32_t    on;
 };
 
-hipError_t launchAlignSearch(const AlignSearchArgs& a, hipStream_t stream);
+// The Viterbi call (gmm_kernels_align.hip)
+struct AlignArgs : AlignBatch, AlignTable {
+    float           pruning;
+    uint32_t*       cells;  // the backpointers: (ordinal << 16) | source state per (frame, state) cell
+    uint32_t *      outMixture, *outState, *outArc;  // [table columns] or NULL
+    float*          outScore;                        // [nSegments] or NULL
+    uint32_t*       outHypotheses;                   // [nSegments] or NULL
+    AlignSearchCall search;
+};
+
+// the kernel with or without the retry loop and the n-best step, as a.search.on says
+hipError_t launchAlign(const AlignArgs& a, hipStream_t stream);
 
 // The Baum-Welch call (gmm_kernels_align_posterior.hip).  LDS of a segment's workgroup: two f64 potential rows, two f32
 // score rows and two rows of active marks (GMM_ALIGN_MAX_STATES_POSTERIOR); the rows are rounded up to 64 states
@@ -67,22 +76,16 @@ static_assert(GMM_ALIGN_MAX_STATES_POSTERIOR <= GMM_ALIGN_MAX_STATES, "set_segme
 // the item passes run one wave per frame, kAlignItemWaves of them at most; each has a row of the weight scratch
 constexpr uint32_t kAlignItemWaves = 1024;
 
-struct AlignPosteriorArgs {
-    // the batch
-    const AlignSegment* segments;
-    const uint32_t*     order;
-    const uint32_t *    inOffset, *inSource, *inMixture;
-    const float *       inWeight, *finalWeight;
-    const uint32_t *    arcOffset, *arcTarget, *arcMixture;  // the arcs as given: CSR by global source state
-    const float*        arcWeight;
-    const uint32_t *    groupOffset, *groupMixture, *groupArcOffset, *groupSource, *groupTarget;
-    const float*        groupWeight;
-    const uint32_t *    colSegment, *colFrameOffset;  // the segments by table column, their ordered frames
+struct AlignPosteriorArgs : AlignBatch, AlignTable {
+    // the batch's tables of this mode
+    const uint32_t *arcOffset, *arcTarget, *arcMixture;  // the arcs as given: CSR by global source state
+    const float*    arcWeight;
+    const uint32_t *groupOffset, *groupMixture, *groupArcOffset, *groupSource, *groupTarget;
+    const float*    groupWeight;
+    const uint32_t *colSegment, *colFrameOffset;  // the segments by table column, their ordered frames
     // the call
-    const float* scores;
-    uint32_t     scoreStride, nTableFrames;
-    float        pruning, minPosterior;
-    uint32_t     maxItems;
+    float    pruning, minPosterior;
+    uint32_t maxItems;
     // the scratch: per (frame, state) cell the forward and backward potentials and the active mark; per segment
     // -bw[initial] and whether it has an alignment; per ordered frame the minimum, the inverse sum and the item count
     // (then offset); per item wave a row of rowGroups weights
@@ -101,19 +104,11 @@ struct AlignPosteriorArgs {
     float*    outScore;
     uint32_t* outHypotheses;
     double*   outLogTotal;
-    uint32_t  nSegments, rowStates, nFrames;
+    uint32_t  nFrames;
+    AlignSearchCall search;
 };
 
+// the sweep with or without the retry loop and the n-best step, as a.search.on says, then the item launches
 hipError_t launchAlignPosteriors(const AlignPosteriorArgs& a, hipStream_t stream);
-
-struct AlignPosteriorSearchArgs {
-    AlignPosteriorArgs call;
-    AlignSearch        search;
-    float*             outThreshold;
-    uint32_t*          outIterations;
-};
-
-// the sweep with the retry loop and the n-best step, then the item launches of launchAlignPosteriors as they are
-hipError_t launchAlignPosteriorsSearch(const AlignPosteriorSearchArgs& a, hipStream_t stream);
 
 }  // namespace rasr_gmm

@@ -1,7 +1,11 @@
-// gmm_align_search.hh -- device code shared by the two search kernels (gmm_kernels_align.hip, gmm_kernels_align_posterior.hip):
-// the stop rule of Search::Aligner::feed(vector) (src/Search/Aligner.cc:594-621) and the n-best step of prune
-// (src/Search/Aligner.cc:254-276); the contract is include/rasr_gmm_align.h's ("THE SEARCH").  Included by the kernel
-// units only; the kernels of the fixed-threshold calls use nothing of it.
+// gmm_align_step.hh -- the device code that the Viterbi kernel (gmm_kernels_align.hip) and the Baum-Welch sweep
+// (gmm_kernels_align_posterior.hip) share, with and without the search; included by the two kernel units only.
+//   the step    sync, minStep, kWaves; pruneThreshold, the end of a frame step behind a mode's candidate loop: the
+//               frame's minimum over the wave and the workgroup, the threshold, the n-best step; sumHypotheses
+//   the search  the stop rule of Search::Aligner::feed(vector) (src/Search/Aligner.cc:594-621), the n-best step of prune
+//               (src/Search/Aligner.cc:254-276) and searchPassEnds, the end of a pass; the contract is
+//               include/rasr_gmm_align.h's ("THE SEARCH").  The fixed-threshold instantiations use nothing of it and
+//               have no SearchLds.
 //
 // The n-best step is a k-th-smallest selection over the reached states' scores of the frame's row in LDS, k = n_best:
 //   select   a radix select on the order-preserving u32 image of the scores, most significant digit first, 4 bits a
@@ -22,40 +26,42 @@
 namespace rasr_gmm {
 namespace dev {
 
-constexpr uint32_t kSearchWaves  = kAlignThreads / 64;
-constexpr uint32_t kNBestPasses  = 8, kNBestBins = 16;
-constexpr uint32_t kNBestRounds  = GMM_ALIGN_MAX_STATES / kAlignThreads;  // the rounds of kAlignThreads states of a row
+constexpr uint32_t kWaves       = kAlignThreads / 64;
+constexpr uint32_t kNBestPasses = 8, kNBestBins = 16;
+constexpr uint32_t kNBestRounds = GMM_ALIGN_MAX_STATES / kAlignThreads;  // the rounds of kAlignThreads states of a row
 static_assert(GMM_ALIGN_MAX_STATES % kAlignThreads == 0 && GMM_ALIGN_MAX_STATES_POSTERIOR <= GMM_ALIGN_MAX_STATES,
               "kNBestRounds covers the rows of both modes");
 
-// the static LDS of a search kernel beside the rows and its own redV / redQ: together they have to fit what
+// the static LDS of a search instantiation beside the rows and its own redV / redQ: together they have to fit what
 // include/rasr_gmm_align.h leaves free for the reductions in both modes (1 KiB in Baum-Welch mode)
 struct SearchLds {
-    uint32_t count[kNBestPasses][kNBestBins];    // the digit counters of the radix select
-    uint32_t equal[kNBestRounds][kSearchWaves];  // per round and wave: the states that hold the k-th score
-    uint32_t reached[kSearchWaves];              // the frame's reached states per wave
-    uint32_t stop;                               // the deciding lane's verdict on the pass
+    uint32_t count[kNBestPasses][kNBestBins];  // the digit counters of the radix select
+    uint32_t equal[kNBestRounds][kWaves];      // per round and wave: the states that hold the k-th score
+    uint32_t reached[kWaves];                  // the frame's reached states per wave
+    uint32_t stop;                             // lane 0's verdict on the pass
 };
-// each search kernel asserts on ALL its static LDS (this and its own reduction arrays) beside the largest rows; the
-// dynamic rows start 16-byte aligned behind it
+// each kernel asserts on ALL its static LDS (this and its own reduction arrays) beside the largest rows; the dynamic
+// rows start 16-byte aligned behind it
 constexpr uint32_t kLdsBytes = 64 * 1024, kLdsAlign = 16;
 
-// what a search kernel hands to its segment function; the fixed-threshold kernels pass an empty one
-struct SearchContext {
-    const AlignSearch* search        = nullptr;
-    float*             outThreshold  = nullptr;
-    uint32_t*          outIterations = nullptr;
-    SearchLds*         lds           = nullptr;
-};
-
-template <bool kWave>
-__device__ __forceinline__ void searchSync() {
+// between two phases.  A single-wave segment needs no barrier: one wave's LDS operations complete in order, so the fence
+// only keeps the compiler from moving them (kGlobal: the phases hand over global memory as well)
+template <bool kWave, bool kGlobal = false>
+__device__ __forceinline__ void sync() {
     if constexpr (kWave) {
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        if constexpr (kGlobal)
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        else
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
     } else {
         __syncthreads();
     }
+}
+
+// minimumScore's step: result > score ? score : result (a NaN never enters)
+__device__ __forceinline__ float minStep(float result, float score) {
+    return result > score ? score : result;
 }
 
 // Core::isAlmostEqual(f32, f32) (src/Core/Utility.hh:316-321), left to right
@@ -100,7 +106,7 @@ __device__ __forceinline__ void nBestStep(float* cur, const uint8_t* curMark, ui
     uint32_t* const    count = &s.count[0][0];
     for (uint32_t i = tid; i < kNBestPasses * kNBestBins; i += T)
         count[i] = 0;
-    searchSync<kWave>();
+    sync<kWave>();
 
     // select: after pass p the first 4 (p + 1) bits of the k-th smallest key; k counts inside the keys that share them
     uint32_t prefix = 0, k = nBest, equalCount = 0;
@@ -113,7 +119,7 @@ __device__ __forceinline__ void nBestStep(float* cur, const uint8_t* curMark, ui
                 if ((key & above) == prefix)
                     atomicAdd(&s.count[pass][(key >> shift) & (kNBestBins - 1u)], 1u);
             }
-        searchSync<kWave>();
+        sync<kWave>();
         uint32_t before = 0, digit = kNBestBins - 1u, below = 0, at = 0;
         bool     found = false;
         for (uint32_t d = 0; d < kNBestBins; ++d) {
@@ -159,7 +165,7 @@ __device__ __forceinline__ void nBestStep(float* cur, const uint8_t* curMark, ui
         if constexpr (kWave) {
             running += static_cast<uint32_t>(__popcll(mask));
         } else {
-            for (uint32_t w = 0; w < kSearchWaves; ++w) {
+            for (uint32_t w = 0; w < kWaves; ++w) {
                 const uint32_t c = s.equal[r][w];
                 rank += w < wave ? c : 0u;
                 running += c;
@@ -168,6 +174,95 @@ __device__ __forceinline__ void nBestStep(float* cur, const uint8_t* curMark, ui
         if (mine && (key > prefix || (eq && rank >= k)))
             cur[q] = demoted;
     }
+}
+
+// The end of a frame step, behind the candidate loop of the mode: every lane has written the scores `cur` and reached
+// marks `curMark` of its states and brings their minimum `mn` (minStep from FLT_MAX) and, in a search, their number.
+// Reduces both across the lanes (shuffles inside a wave, redV and the search's LDS across the waves, one barrier), forms
+// threshold = minimum + pruning and, in a search that reached more than n_best states, runs the n-best step.  Returns
+// the threshold; the caller's keep loop clears the marks above it.
+template <bool kWave, bool kSearch>
+__device__ __forceinline__ float pruneThreshold(float mn, uint32_t nReached, float pruning, float* cur,
+                                                const uint8_t* curMark, uint32_t n, uint32_t nBest, float* redV,
+                                                SearchLds* s) {
+    for (uint32_t d = 32; d; d >>= 1) {
+        mn = minStep(mn, __shfl_xor(mn, d));
+        if constexpr (kSearch)
+            nReached += __shfl_xor(nReached, d);
+    }
+    if constexpr (!kWave) {
+        const uint32_t wave = threadIdx.x >> 6;
+        if ((threadIdx.x & 63u) == 0) {
+            redV[wave] = mn;
+            if constexpr (kSearch)
+                s->reached[wave] = nReached;
+        }
+        __syncthreads();
+        mn = FLT_MAX;
+        for (uint32_t w = 0; w < kWaves; ++w)
+            mn = minStep(mn, redV[w]);
+        if constexpr (kSearch) {
+            nReached = 0;
+            for (uint32_t w = 0; w < kWaves; ++w)
+                nReached += s->reached[w];
+        }
+    }
+    const float threshold = __fadd_rn(mn, pruning);
+    if constexpr (kSearch) {
+        // uniform over the workgroup: every lane holds the same count
+        if (nBest < nReached)
+            nBestStep<kWave>(cur, curMark, n, nBest, __fadd_rn(threshold, 1.0f), *s);
+    }
+    return threshold;
+}
+
+// the lanes' counts of kept hypotheses, summed over the wave and, through red[kWaves] and one barrier, the workgroup
+// (the sweep's; the Viterbi kernel's sum rides on the barrier of its final scan)
+template <bool kWave>
+__device__ __forceinline__ uint32_t sumHypotheses(uint32_t hypotheses, uint32_t* red) {
+    for (uint32_t d = 32; d; d >>= 1)
+        hypotheses += __shfl_xor(hypotheses, d);
+    if constexpr (!kWave) {
+        if ((threadIdx.x & 63u) == 0)
+            red[threadIdx.x >> 6] = hypotheses;
+        __syncthreads();
+        hypotheses = 0;
+        for (uint32_t w = 0; w < kWaves; ++w)
+            hypotheses += red[w];
+    }
+    return hypotheses;
+}
+
+// The end of a search pass at `pruning`, called by all lanes.  kEveryLane (one wave whose lanes all hold the pass's score
+// and hypotheses): every lane decides alike (searchStops), without LDS.  Otherwise (score, hypotheses) are lane 0's: it
+// decides (`previous` is its own) and hands the verdict over in LDS; the other lanes' next threshold is the same one f32
+// product of values every lane holds.  After the last pass lane 0 writes the segment's threshold and iterations.
+// Returns whether the pass was the last.
+template <bool kWave, bool kEveryLane>
+__device__ __forceinline__ bool searchPassEnds(const AlignSearchCall& sc, SearchLds& s, uint32_t segment, float score,
+                                               uint32_t hypotheses, uint32_t nFrames, uint32_t& iterations,
+                                               float& previous, float& pruning) {
+    static_assert(kWave || !kEveryLane, "only a single wave decides in every lane");
+    const float at = pruning;
+    ++iterations;
+    bool stop;
+    if constexpr (kEveryLane) {
+        stop = searchStops(sc.rule, score, hypotheses, nFrames, iterations, previous, pruning);
+    } else {
+        if (threadIdx.x == 0)
+            s.stop = searchStops(sc.rule, score, hypotheses, nFrames, iterations, previous, pruning);
+        sync<kWave>();
+        stop = s.stop != 0;
+        if (!stop && threadIdx.x != 0)
+            pruning = __fmul_rn(pruning, sc.rule.factor);
+    }
+    if (stop && threadIdx.x == 0) {
+        if (sc.outThreshold)
+            sc.outThreshold[segment] = at;
+        if (sc.outIterations)
+            sc.outIterations[segment] = iterations;
+    }
+    return stop;
 }
 
 }  // namespace dev

@@ -22,40 +22,17 @@
 // one dependent load per frame, and leaves (ordinal, state) of frame t in the frame's cell 0; all lanes then resolve
 // these to the arc, its mixture and its target and write the outputs.
 // Every floating-point operation is an _rn intrinsic (the unit is also built with -ffp-contract=off).
-// alignViterbiSearch (gmm_aligner_align_search_*) is the same segment function with the search flag on: the retry loop
-// of feed(vector) around the frame loop, the n-best step of gmm_align_search.hh in the prune; alignViterbi's code does
-// not change with it.
-#include "gmm_align.hh"
-#include "gmm_align_search.hh"
-
-#include <cfloat>
+// The end of the frame step (minimum, threshold) and everything of the search are gmm_align_step.hh's, shared with the
+// Baum-Welch sweep; the scan, the prune's keep loop and the final scan (which also sums the hypotheses) are this unit's.
+// alignViterbi<true> (gmm_aligner_align_search_*) is the same kernel with the search on: the retry loop of feed(vector)
+// around the frame loop, the n-best step in the prune; alignViterbi<false> has none of it, nor its LDS.
+#include "gmm_align_step.hh"
 
 namespace rasr_gmm {
 namespace dev {
 namespace {
 
-constexpr uint32_t kNone  = 0xffffffffu;
-constexpr uint32_t kWaves = kAlignThreads / 64;
-
-// between two phases.  A single-wave segment needs no barrier: one wave's LDS operations complete in order, so the fence
-// only keeps the compiler from moving them (kGlobal: the phases hand over global memory, the backpointers)
-template <bool kWave, bool kGlobal = false>
-__device__ __forceinline__ void sync() {
-    if constexpr (kWave) {
-        if constexpr (kGlobal)
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        else
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    } else {
-        __syncthreads();
-    }
-}
-
-// minimumScore's step: result > score ? score : result (a NaN never enters)
-__device__ __forceinline__ float minStep(float result, float score) {
-    return result > score ? score : result;
-}
+constexpr uint32_t kNone = 0xffffffffu;
 
 // the final scan's order: a smaller value first, the lower state among equal values
 __device__ __forceinline__ void finalStep(float& v, uint32_t& q, float v2, uint32_t q2) {
@@ -68,7 +45,7 @@ __device__ __forceinline__ void finalStep(float& v, uint32_t& q, float v2, uint3
 // function is the one pass at a.pruning
 template <bool kWave, bool kSearch>
 __device__ __forceinline__ void alignSegment(const AlignArgs& a, const uint32_t segment, float* rows, uint8_t* marks,
-                                             float* redV, uint32_t* redQ, const SearchContext& sc) {
+                                             float* redV, uint32_t* redQ, SearchLds* searchLds) {
     constexpr uint32_t T   = kWave ? 64u : kAlignThreads;
     const AlignSegment sg  = a.segments[segment];
     const uint32_t     tid = threadIdx.x, n = sg.nStates, gb = sg.stateBegin;
@@ -77,7 +54,7 @@ __device__ __forceinline__ void alignSegment(const AlignArgs& a, const uint32_t 
     float              pruning = a.pruning, previous = FLT_MAX, best;
     uint32_t           iterations = 0, bestState, hypotheses;
     if constexpr (kSearch)
-        pruning = sc.search->minPruning;
+        pruning = a.search.rule.minPruning;
 
     for (;;) {  // the passes of the search; one without it
         // start: the initial state alone, with score 0
@@ -124,33 +101,8 @@ __device__ __forceinline__ void alignSegment(const AlignArgs& a, const uint32_t 
                 if constexpr (kSearch)
                     nReached += reached;
             }
-            for (uint32_t d = 32; d; d >>= 1) {
-                mn = minStep(mn, __shfl_xor(mn, d));
-                if constexpr (kSearch)
-                    nReached += __shfl_xor(nReached, d);
-            }
-            if constexpr (!kWave) {
-                if (lane == 0) {
-                    redV[wave] = mn;
-                    if constexpr (kSearch)
-                        sc.lds->reached[wave] = nReached;
-                }
-                __syncthreads();
-                mn = FLT_MAX;
-                for (uint32_t w = 0; w < kWaves; ++w)
-                    mn = minStep(mn, redV[w]);
-                if constexpr (kSearch) {
-                    nReached = 0;
-                    for (uint32_t w = 0; w < kWaves; ++w)
-                        nReached += sc.lds->reached[w];
-                }
-            }
-            const float threshold = __fadd_rn(mn, pruning);
-            if constexpr (kSearch) {
-                // uniform over the workgroup: every lane holds the same count
-                if (sc.search->nBest < nReached)
-                    nBestStep<kWave>(cur, curMark, n, sc.search->nBest, __fadd_rn(threshold, 1.0f), *sc.lds);
-            }
+            const float threshold = pruneThreshold<kWave, kSearch>(mn, nReached, pruning, cur, curMark, n,
+                                                                   a.search.rule.nBest, redV, searchLds);
             for (uint32_t q = tid; q < n; q += T)
                 if (curMark[q]) {
                     const bool keep = cur[q] <= threshold;
@@ -179,7 +131,7 @@ __device__ __forceinline__ void alignSegment(const AlignArgs& a, const uint32_t 
             hypotheses += __shfl_xor(hypotheses, d);
         }
         if constexpr (!kWave) {
-            // redV's last readers are behind the last frame's second barrier
+            // redV's last readers are behind the last frame's second barrier; the hypotheses ride on the scan's barrier
             if (lane == 0) {
                 redV[wave]          = best;
                 redQ[wave]          = bestState;
@@ -194,36 +146,14 @@ __device__ __forceinline__ void alignSegment(const AlignArgs& a, const uint32_t 
                 hypotheses += redQ[kWaves + w];
             }
         }
-        if constexpr (!kSearch) {
-            break;
-        } else {
-            // the pass is over: every lane holds its score and hypothesis count.  One wave decides in every lane alike;
-            // in the workgroup form lane 0 does and hands the verdict over in LDS.  The next pass overwrites the
-            // backpointers
-            const float at = pruning;
-            ++iterations;
-            bool stop;
-            if constexpr (kWave) {
-                stop = searchStops(*sc.search, best, hypotheses, sg.nFrames, iterations, previous, pruning);
-            } else {
-                if (tid == 0)
-                    sc.lds->stop = searchStops(*sc.search, best, hypotheses, sg.nFrames, iterations, previous, pruning);
-                __syncthreads();
-                stop = sc.lds->stop != 0;
-                // lane 0's next threshold is one f32 product of values every lane holds
-                if (!stop && tid != 0)
-                    pruning = __fmul_rn(pruning, sc.search->factor);
-            }
-            if (stop) {
-                if (tid == 0) {
-                    if (sc.outThreshold)
-                        sc.outThreshold[segment] = at;
-                    if (sc.outIterations)
-                        sc.outIterations[segment] = iterations;
-                }
-                break;
-            }
+        // the pass is over: every lane holds its score and hypothesis count, so one wave decides in every lane alike.
+        // The next pass overwrites the backpointers
+        if constexpr (kSearch) {
+            if (!searchPassEnds<kWave, kWave>(a.search, *searchLds, segment, best, hypotheses, sg.nFrames, iterations,
+                                              previous, pruning))
+                continue;
         }
+        break;
     }
     if (tid == 0) {
         if (a.outScore)
@@ -272,45 +202,29 @@ __device__ __forceinline__ void alignSegment(const AlignArgs& a, const uint32_t 
 
 }  // namespace
 
+// one workgroup per segment; in a search each with its own number of passes
+template <bool kSearch>
 __global__ __launch_bounds__(kAlignThreads) void alignViterbi(AlignArgs a) {
     extern __shared__ __align__(16) unsigned char lds[];
     __shared__ float    redV[kWaves];
     __shared__ uint32_t redQ[2 * kWaves];
-    float* const        rows  = reinterpret_cast<float*>(lds);
-    uint8_t* const      marks = lds + 2u * a.rowStates * sizeof(float);
-    const uint32_t      segment = a.order[blockIdx.x];
+    static_assert(GMM_ALIGN_MAX_STATES * kAlignLdsBytesPerState + sizeof(redV) + sizeof(redQ) + sizeof(SearchLds) +
+                                  2 * kLdsAlign <= kLdsBytes,
+                  "the rows of the largest segment fit beside all static LDS, the search's included");
+    SearchLds* searchLds = nullptr;
+    if constexpr (kSearch) {
+        __shared__ SearchLds s;
+        searchLds = &s;
+    }
+    float* const   rows  = reinterpret_cast<float*>(lds);
+    uint8_t* const marks = lds + 2u * a.rowStates * sizeof(float);
+    const uint32_t segment = a.order[blockIdx.x];
     // uniform over the workgroup: either wave 0 alone, with no barrier, or all waves through every barrier
     if (a.segments[segment].nStates <= kAlignWaveStates) {
         if (threadIdx.x < 64)
-            alignSegment<true, false>(a, segment, rows, marks, redV, redQ, SearchContext{});
+            alignSegment<true, kSearch>(a, segment, rows, marks, redV, redQ, searchLds);
     } else {
-        alignSegment<false, false>(a, segment, rows, marks, redV, redQ, SearchContext{});
-    }
-}
-
-// the search call: the same workgroup per segment, each with its own number of passes
-__global__ __launch_bounds__(kAlignThreads) void alignViterbiSearch(AlignSearchArgs sa) {
-    extern __shared__ __align__(16) unsigned char lds[];
-    __shared__ float     redV[kWaves];
-    __shared__ uint32_t  redQ[2 * kWaves];
-    __shared__ SearchLds searchLds;
-    static_assert(GMM_ALIGN_MAX_STATES * kAlignLdsBytesPerState + sizeof(redV) + sizeof(redQ) + sizeof(SearchLds) +
-                                  2 * kLdsAlign <= kLdsBytes,
-                  "the rows of the largest segment fit beside all static LDS of the search kernel");
-    const AlignArgs&     a = sa.call;
-    float* const         rows  = reinterpret_cast<float*>(lds);
-    uint8_t* const       marks = lds + 2u * a.rowStates * sizeof(float);
-    const uint32_t       segment = a.order[blockIdx.x];
-    SearchContext        sc;
-    sc.search        = &sa.search;
-    sc.outThreshold  = sa.outThreshold;
-    sc.outIterations = sa.outIterations;
-    sc.lds           = &searchLds;
-    if (a.segments[segment].nStates <= kAlignWaveStates) {
-        if (threadIdx.x < 64)
-            alignSegment<true, true>(a, segment, rows, marks, redV, redQ, sc);
-    } else {
-        alignSegment<false, true>(a, segment, rows, marks, redV, redQ, sc);
+        alignSegment<false, kSearch>(a, segment, rows, marks, redV, redQ, searchLds);
     }
 }
 
@@ -320,15 +234,8 @@ hipError_t launchAlign(const AlignArgs& a, hipStream_t stream) {
     if (a.nSegments == 0)
         return hipSuccess;
     const size_t ldsBytes = static_cast<size_t>(a.rowStates) * kAlignLdsBytesPerState;
-    hipLaunchKernelGGL(dev::alignViterbi, dim3(a.nSegments), dim3(kAlignThreads), ldsBytes, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launchAlignSearch(const AlignSearchArgs& a, hipStream_t stream) {
-    if (a.call.nSegments == 0)
-        return hipSuccess;
-    const size_t ldsBytes = static_cast<size_t>(a.call.rowStates) * kAlignLdsBytesPerState;
-    hipLaunchKernelGGL(dev::alignViterbiSearch, dim3(a.call.nSegments), dim3(kAlignThreads), ldsBytes, stream, a);
+    const auto   kernel   = a.search.on ? dev::alignViterbi<true> : dev::alignViterbi<false>;
+    hipLaunchKernelGGL(kernel, dim3(a.nSegments), dim3(kAlignThreads), ldsBytes, stream, a);
     return hipGetLastError();
 }
 

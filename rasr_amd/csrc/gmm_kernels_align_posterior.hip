@@ -26,38 +26,18 @@
 //   alignPosteriorItems<true>   the item pass again with the minimum and 1 / sum known: writes the compact list.
 // Every f32 / f64 add, subtract, multiply and divide is an _rn intrinsic (the unit is also built with
 // -ffp-contract=off); exp and log1p are the device library's f64 functions.  No atomics.
-// alignPosteriorSweepSearch (gmm_aligner_posteriors_search_*) is the sweep with the search flag on: the retry loop of
-// feed(vector) around forward and end, the n-best step of gmm_align_search.hh in the prune (its digit counters are
-// integer LDS atomics); the other four launches are shared, and alignPosteriorSweep's code does not change with it.
-#include "gmm_align.hh"
-#include "gmm_align_search.hh"
+// The end of the forward frame step (minimum, threshold), the sum of the hypotheses and everything of the search are
+// gmm_align_step.hh's, shared with the Viterbi kernel; posterior64's batch collect is written once, batchCollect64.
+// alignPosteriorSweep<true> (gmm_aligner_posteriors_search_*) is the sweep with the search on: the retry loop of
+// feed(vector) around forward and end, the n-best step in the prune (its digit counters are integer LDS atomics);
+// alignPosteriorSweep<false> has none of it, nor its LDS.  The other four launches serve both.
+#include "gmm_align_step.hh"
 
-#include <cfloat>
 #include <cmath>
 
 namespace rasr_gmm {
 namespace dev {
 namespace {
-
-constexpr uint32_t kWaves = kAlignThreads / 64;
-
-// between two phases; see gmm_kernels_align.hip
-template <bool kWave, bool kGlobal = false>
-__device__ __forceinline__ void sync() {
-    if constexpr (kWave) {
-        if constexpr (kGlobal)
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        else
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    } else {
-        __syncthreads();
-    }
-}
-
-__device__ __forceinline__ float minStep(float result, float score) {
-    return result > score ? score : result;
-}
 
 // LogSemiring<f32>::collect: FLT_MAX is the zero; min - log1p(exp(min - max)), the transcendentals in f64 on the widened
 // difference, their value rounded once to f32
@@ -83,17 +63,58 @@ __device__ __forceinline__ double close64(double mn, double sum) {
     return v < DBL_MAX ? v : DBL_MAX;
 }
 
+// posterior64's batch collect over the arcs k0 .. k1 of a state: a <= scan for the minimum of score(k) over the arcs
+// with active(k), then the sum of exp(minimum - score(k)) over the other active arcs, closed.  visit(k) runs once per
+// active arc, in arc order, beside the scan
+struct NoVisit {
+    __device__ void operator()(uint32_t) const {}
+};
+template <class Active, class Score, class Visit = NoVisit>
+__device__ __forceinline__ double batchCollect64(uint32_t k0, uint32_t k1, Active active, Score score,
+                                                 Visit visit = Visit{}) {
+    double   potMin = DBL_MAX;
+    uint32_t kMin = k1, nActive = 0;
+    for (uint32_t k = k0; k < k1; ++k)
+        if (active(k)) {
+            visit(k);
+            ++nActive;
+            const double s = score(k);
+            if (s <= potMin) {
+                potMin = s;
+                kMin   = k;
+            }
+        }
+    double sum = 0.0;
+    if (nActive > 1)
+        for (uint32_t k = k0; k < k1; ++k)
+            if (k != kMin && active(k))
+                sum = __dadd_rn(sum, exp(__dsub_rn(potMin, score(k))));
+    return close64(potMin, sum);
+}
+
+// posterior64's backward step of the (global) source state: its arcs, in arc order, into the states active in the next
+// frame, whose marks, potentials and table column are given
+__device__ __forceinline__ double backwardState(const AlignPosteriorArgs& a, uint32_t state, const uint8_t* nextMark,
+                                                const double* next, const float* column) {
+    return batchCollect64(
+            a.arcOffset[state], a.arcOffset[state + 1], [&](uint32_t k) { return nextMark[a.arcTarget[k]] != 0; },
+            [&](uint32_t k) {
+                const float arcScore =
+                        __fadd_rn(a.arcWeight[k], column[static_cast<size_t>(a.arcMixture[k]) * a.scoreStride]);
+                return extend64(next[a.arcTarget[k]], arcScore);
+            });
+}
+
 // kSearch: the forward part and the end run inside the retry loop of feed(vector), with the n-best step in the prune; a
 // pass overwrites the cells of the one before, and the backward sweep runs once, over the last pass's.  Without it the
 // function is the one pass at a.pruning
 template <bool kWave, bool kSearch>
 __device__ __forceinline__ void sweepSegment(const AlignPosteriorArgs& a, const uint32_t segment, double* rows64,
                                              float* rows32, uint8_t* marks, float* redV, uint32_t* redQ,
-                                             const SearchContext& sc) {
+                                             SearchLds* searchLds) {
     constexpr uint32_t T   = kWave ? 64u : kAlignThreads;
     const AlignSegment sg  = a.segments[segment];
     const uint32_t     tid = threadIdx.x, n = sg.nStates, gb = sg.stateBegin, R = a.rowStates;
-    const uint32_t     wave = tid >> 6, lane = tid & 63u;
     double* const      fwPot = a.fwPot + sg.cellBegin;
     double* const      bwPot = a.bwPot + sg.cellBegin;
     uint8_t* const     mark  = a.mark + sg.cellBegin;
@@ -101,7 +122,7 @@ __device__ __forceinline__ void sweepSegment(const AlignPosteriorArgs& a, const 
     float              pruning = a.pruning, previous = FLT_MAX;  // previous: lane 0's
     uint32_t           iterations = 0;
     if constexpr (kSearch)
-        pruning = sc.search->minPruning;
+        pruning = a.search.rule.minPruning;
 
     for (;;) {  // the passes of the search; one without it
         for (uint32_t q = tid; q < n; q += T) {
@@ -129,36 +150,17 @@ __device__ __forceinline__ void sweepSegment(const AlignPosteriorArgs& a, const 
                 const uint32_t j0 = a.inOffset[gb + q], j1 = a.inOffset[gb + q + 1];
                 bool           reached = false;
                 float          score = 0.0f;
-                double         potMin = DBL_MAX;
-                uint32_t       jMin = j1, nActive = 0;
-                for (uint32_t j = j0; j < j1; ++j) {
-                    const uint32_t p = a.inSource[j];
-                    const float    w = a.inWeight[j];
-                    const float    e = column[static_cast<size_t>(a.inMixture[j]) * a.scoreStride];
-                    if (prevMark[p]) {
-                        const float arcScore = __fadd_rn(w, e);
-                        const float cand     = __fadd_rn(prev[p], arcScore);
-                        score                = reached ? collect32(score, cand) : cand;
-                        reached              = true;
-                        ++nActive;
-                        const double s = extend64(prevPot[p], arcScore);
-                        if (s <= potMin) {
-                            potMin = s;
-                            jMin   = j;
-                        }
-                    }
-                }
-                double sum = 0.0;
-                if (nActive > 1)
-                    for (uint32_t j = j0; j < j1; ++j) {
-                        const uint32_t p = a.inSource[j];
-                        if (j != jMin && prevMark[p]) {
-                            const float arcScore =
-                                    __fadd_rn(a.inWeight[j], column[static_cast<size_t>(a.inMixture[j]) * a.scoreStride]);
-                            sum = __dadd_rn(sum, exp(__dsub_rn(potMin, extend64(prevPot[p], arcScore))));
-                        }
-                    }
-                const double pot = close64(potMin, sum);
+                auto           arcScore = [&](uint32_t j) {
+                    return __fadd_rn(a.inWeight[j], column[static_cast<size_t>(a.inMixture[j]) * a.scoreStride]);
+                };
+                const double pot = batchCollect64(
+                        j0, j1, [&](uint32_t j) { return prevMark[a.inSource[j]] != 0; },
+                        [&](uint32_t j) { return extend64(prevPot[a.inSource[j]], arcScore(j)); },
+                        [&](uint32_t j) {
+                            const float cand = __fadd_rn(prev[a.inSource[j]], arcScore(j));
+                            score            = reached ? collect32(score, cand) : cand;
+                            reached          = true;
+                        });
                 cur[q]           = score;
                 curPot[q]        = pot;
                 curMark[q]       = reached;
@@ -168,33 +170,8 @@ __device__ __forceinline__ void sweepSegment(const AlignPosteriorArgs& a, const 
                 if constexpr (kSearch)
                     nReached += reached;
             }
-            for (uint32_t d = 32; d; d >>= 1) {
-                mn = minStep(mn, __shfl_xor(mn, d));
-                if constexpr (kSearch)
-                    nReached += __shfl_xor(nReached, d);
-            }
-            if constexpr (!kWave) {
-                if (lane == 0) {
-                    redV[wave] = mn;
-                    if constexpr (kSearch)
-                        sc.lds->reached[wave] = nReached;
-                }
-                __syncthreads();
-                mn = FLT_MAX;
-                for (uint32_t w = 0; w < kWaves; ++w)
-                    mn = minStep(mn, redV[w]);
-                if constexpr (kSearch) {
-                    nReached = 0;
-                    for (uint32_t w = 0; w < kWaves; ++w)
-                        nReached += sc.lds->reached[w];
-                }
-            }
-            const float threshold = __fadd_rn(mn, pruning);
-            if constexpr (kSearch) {
-                // uniform over the workgroup: every lane holds the same count
-                if (sc.search->nBest < nReached)
-                    nBestStep<kWave>(cur, curMark, n, sc.search->nBest, __fadd_rn(threshold, 1.0f), *sc.lds);
-            }
+            const float threshold = pruneThreshold<kWave, kSearch>(mn, nReached, pruning, cur, curMark, n,
+                                                                   a.search.rule.nBest, redV, searchLds);
             for (uint32_t q = tid; q < n; q += T) {
                 bool keep = false;
                 if (curMark[q]) {
@@ -207,25 +184,13 @@ __device__ __forceinline__ void sweepSegment(const AlignPosteriorArgs& a, const 
             sync<kWave>();
         }
 
-        for (uint32_t d = 32; d; d >>= 1)
-            hypotheses += __shfl_xor(hypotheses, d);
-        if constexpr (!kWave) {
-            if (lane == 0)
-                redQ[wave] = hypotheses;
-            __syncthreads();
-            hypotheses = 0;
-            for (uint32_t w = 0; w < kWaves; ++w)
-                hypotheses += redQ[w];
-        }
+        hypotheses = sumHypotheses<kWave>(hypotheses, redQ);
 
-        // end: alignmentScore() over the active final states in ascending order; in a search lane 0 then decides whether
-        // the pass was the last, and only the last one's results are written
-        const float at = pruning;
-        if constexpr (kSearch)
-            ++iterations;
+        // end: lane 0's alignmentScore() over the active final states in ascending order; in a search it then decides
+        // whether the pass was the last, and only the last one's results are written
+        float    result = FLT_MAX;
+        uint32_t has = 0;
         if (tid == 0) {
-            float    result = FLT_MAX;
-            uint32_t has = 0;
             for (uint32_t q = 0; q < n; ++q)
                 if (marks[last + q]) {
                     const float fw = a.finalWeight[gb + q];
@@ -237,38 +202,24 @@ __device__ __forceinline__ void sweepSegment(const AlignPosteriorArgs& a, const 
                 }
             if (!has)
                 result = FLT_MAX;
-            bool stop = true;
-            if constexpr (kSearch) {
-                stop = searchStops(*sc.search, result, hypotheses, sg.nFrames, iterations, previous, pruning);
-                sc.lds->stop = stop;
-                if (stop) {
-                    if (sc.outThreshold)
-                        sc.outThreshold[segment] = at;
-                    if (sc.outIterations)
-                        sc.outIterations[segment] = iterations;
-                }
-            }
-            if (stop) {
-                if (a.outScore)
-                    a.outScore[segment] = result;
-                if (a.outHypotheses)
-                    a.outHypotheses[segment] = hypotheses;
-                a.segHas[segment] = has;
-            }
-            redQ[kWaves] = has;
         }
-        // the marks of the scratch are read below by other lanes than wrote them
-        sync<kWave, true>();
         if constexpr (kSearch) {
-            if (!sc.lds->stop) {
-                // lane 0's next threshold is one f32 product of values every lane holds
-                if (tid != 0)
-                    pruning = __fmul_rn(pruning, sc.search->factor);
+            if (!searchPassEnds<kWave, false>(a.search, *searchLds, segment, result, hypotheses, sg.nFrames, iterations,
+                                              previous, pruning))
                 continue;
-            }
+        }
+        if (tid == 0) {
+            if (a.outScore)
+                a.outScore[segment] = result;
+            if (a.outHypotheses)
+                a.outHypotheses[segment] = hypotheses;
+            a.segHas[segment] = has;
+            redQ[kWaves]      = has;
         }
         break;
     }
+    // redQ[kWaves] and the marks of the scratch are read below by other lanes than wrote them
+    sync<kWave, true>();
     if (!redQ[kWaves]) {
         if (tid == 0) {
             a.segTotalInv[segment] = 0.0;
@@ -298,69 +249,15 @@ __device__ __forceinline__ void sweepSegment(const AlignPosteriorArgs& a, const 
         const uint8_t* const nextMark = mark + row + n;
         const float* const   column = a.scores + sg.frameBegin + t + 1;
         for (uint32_t p = tid; p < n; p += T) {
-            double v = DBL_MAX;
-            if (mark[row + p]) {
-                const uint32_t a0 = a.arcOffset[gb + p], a1 = a.arcOffset[gb + p + 1];
-                double         potMin = DBL_MAX;
-                uint32_t       aMin = a1, nActive = 0;
-                for (uint32_t k = a0; k < a1; ++k) {
-                    const uint32_t q = a.arcTarget[k];
-                    if (nextMark[q]) {
-                        const float arcScore =
-                                __fadd_rn(a.arcWeight[k], column[static_cast<size_t>(a.arcMixture[k]) * a.scoreStride]);
-                        const double s = extend64(next[q], arcScore);
-                        ++nActive;
-                        if (s <= potMin) {
-                            potMin = s;
-                            aMin   = k;
-                        }
-                    }
-                }
-                double sum = 0.0;
-                if (nActive > 1)
-                    for (uint32_t k = a0; k < a1; ++k) {
-                        const uint32_t q = a.arcTarget[k];
-                        if (k != aMin && nextMark[q]) {
-                            const float arcScore = __fadd_rn(
-                                    a.arcWeight[k], column[static_cast<size_t>(a.arcMixture[k]) * a.scoreStride]);
-                            sum = __dadd_rn(sum, exp(__dsub_rn(potMin, extend64(next[q], arcScore))));
-                        }
-                    }
-                v = close64(potMin, sum);
-            }
+            const double v = mark[row + p] ? backwardState(a, gb + p, nextMark, next, column) : DBL_MAX;
             cur[p]         = v;
             bwPot[row + p] = v;
         }
         sync<kWave>();
     }
-    // bw[initial]: the initial state's arcs into frame 0
+    // bw[initial]: the backward step of the initial state with frame 0 as the next frame
     if (tid == 0) {
-        const double* const next = rows64;  // frame 0's row
-        const float* const  column = a.scores + sg.frameBegin;
-        const uint32_t      a0 = a.arcOffset[gb + sg.initial], a1 = a.arcOffset[gb + sg.initial + 1];
-        double              potMin = DBL_MAX, sum = 0.0;
-        uint32_t            aMin = a1;
-        for (uint32_t k = a0; k < a1; ++k) {
-            const uint32_t q = a.arcTarget[k];
-            if (mark[q]) {
-                const float arcScore =
-                        __fadd_rn(a.arcWeight[k], column[static_cast<size_t>(a.arcMixture[k]) * a.scoreStride]);
-                const double s = extend64(next[q], arcScore);
-                if (s <= potMin) {
-                    potMin = s;
-                    aMin   = k;
-                }
-            }
-        }
-        for (uint32_t k = a0; k < a1; ++k) {
-            const uint32_t q = a.arcTarget[k];
-            if (k != aMin && mark[q]) {
-                const float arcScore =
-                        __fadd_rn(a.arcWeight[k], column[static_cast<size_t>(a.arcMixture[k]) * a.scoreStride]);
-                sum = __dadd_rn(sum, exp(__dsub_rn(potMin, extend64(next[q], arcScore))));
-            }
-        }
-        const double total     = close64(potMin, sum);
+        const double total     = backwardState(a, gb + sg.initial, mark, rows64, a.scores + sg.frameBegin);
         a.segTotalInv[segment] = -total;
         if (a.outLogTotal)
             a.outLogTotal[segment] = total;
@@ -383,46 +280,29 @@ __device__ __forceinline__ uint32_t frameSegment(const AlignPosteriorArgs& a, ui
 
 }  // namespace
 
+// one workgroup per segment; in a search each with its own number of forward passes
+template <bool kSearch>
 __global__ __launch_bounds__(kAlignThreads) void alignPosteriorSweep(AlignPosteriorArgs a) {
     extern __shared__ __align__(16) unsigned char lds[];
     __shared__ float    redV[kWaves];
     __shared__ uint32_t redQ[kWaves + 1];
-    double* const       rows64 = reinterpret_cast<double*>(lds);
-    float* const        rows32 = reinterpret_cast<float*>(lds + 2u * a.rowStates * sizeof(double));
-    uint8_t* const      marks  = lds + 2u * a.rowStates * (sizeof(double) + sizeof(float));
-    const uint32_t      segment = a.order[blockIdx.x];
-    if (a.segments[segment].nStates <= kAlignWaveStates) {
-        if (threadIdx.x < 64)
-            sweepSegment<true, false>(a, segment, rows64, rows32, marks, redV, redQ, SearchContext{});
-    } else {
-        sweepSegment<false, false>(a, segment, rows64, rows32, marks, redV, redQ, SearchContext{});
-    }
-}
-
-// the search call's sweep: the same workgroup per segment, each with its own number of forward passes
-__global__ __launch_bounds__(kAlignThreads) void alignPosteriorSweepSearch(AlignPosteriorSearchArgs sa) {
-    extern __shared__ __align__(16) unsigned char lds[];
-    __shared__ float          redV[kWaves];
-    __shared__ uint32_t       redQ[kWaves + 1];
-    __shared__ SearchLds      searchLds;
     static_assert(((GMM_ALIGN_MAX_STATES_POSTERIOR + 63u) & ~63u) * kAlignPosteriorLdsBytesPerState + sizeof(redV) +
                                   sizeof(redQ) + sizeof(SearchLds) + 2 * kLdsAlign <= kLdsBytes,
-                  "the rows of the largest segment fit beside all static LDS of the search sweep");
-    const AlignPosteriorArgs& a = sa.call;
-    double* const             rows64 = reinterpret_cast<double*>(lds);
-    float* const              rows32 = reinterpret_cast<float*>(lds + 2u * a.rowStates * sizeof(double));
-    uint8_t* const            marks  = lds + 2u * a.rowStates * (sizeof(double) + sizeof(float));
-    const uint32_t            segment = a.order[blockIdx.x];
-    SearchContext             sc;
-    sc.search        = &sa.search;
-    sc.outThreshold  = sa.outThreshold;
-    sc.outIterations = sa.outIterations;
-    sc.lds           = &searchLds;
+                  "the rows of the largest segment fit beside all static LDS, the search's included");
+    SearchLds* searchLds = nullptr;
+    if constexpr (kSearch) {
+        __shared__ SearchLds s;
+        searchLds = &s;
+    }
+    double* const  rows64 = reinterpret_cast<double*>(lds);
+    float* const   rows32 = reinterpret_cast<float*>(lds + 2u * a.rowStates * sizeof(double));
+    uint8_t* const marks  = lds + 2u * a.rowStates * (sizeof(double) + sizeof(float));
+    const uint32_t segment = a.order[blockIdx.x];
     if (a.segments[segment].nStates <= kAlignWaveStates) {
         if (threadIdx.x < 64)
-            sweepSegment<true, true>(a, segment, rows64, rows32, marks, redV, redQ, sc);
+            sweepSegment<true, kSearch>(a, segment, rows64, rows32, marks, redV, redQ, searchLds);
     } else {
-        sweepSegment<false, true>(a, segment, rows64, rows32, marks, redV, redQ, sc);
+        sweepSegment<false, kSearch>(a, segment, rows64, rows32, marks, redV, redQ, searchLds);
     }
 }
 
@@ -610,10 +490,12 @@ __global__ __launch_bounds__(kAlignThreads) void alignPosteriorColumns(AlignPost
 
 }  // namespace dev
 
-namespace {
-
-// the launches behind the sweep, the same for both calls
-hipError_t launchItems(const AlignPosteriorArgs& a, hipStream_t stream) {
+hipError_t launchAlignPosteriors(const AlignPosteriorArgs& a, hipStream_t stream) {
+    if (a.nSegments == 0)
+        return hipSuccess;
+    const size_t ldsBytes = static_cast<size_t>(a.rowStates) * kAlignPosteriorLdsBytesPerState;
+    const auto   sweep    = a.search.on ? dev::alignPosteriorSweep<true> : dev::alignPosteriorSweep<false>;
+    hipLaunchKernelGGL(sweep, dim3(a.nSegments), dim3(kAlignThreads), ldsBytes, stream, a);
     const uint32_t itemWaves = a.nFrames < kAlignItemWaves ? a.nFrames : kAlignItemWaves;
     hipLaunchKernelGGL(dev::alignPosteriorItems<false>, dim3(itemWaves), dim3(64), 0, stream, a);
     hipLaunchKernelGGL(dev::alignPosteriorScan, dim3(1), dim3(kAlignThreads), 0, stream, a);
@@ -624,24 +506,6 @@ hipError_t launchItems(const AlignPosteriorArgs& a, hipStream_t stream) {
     if (a.outItemFrame)
         hipLaunchKernelGGL(dev::alignPosteriorItems<true>, dim3(itemWaves), dim3(64), 0, stream, a);
     return hipGetLastError();
-}
-
-}  // namespace
-
-hipError_t launchAlignPosteriors(const AlignPosteriorArgs& a, hipStream_t stream) {
-    if (a.nSegments == 0)
-        return hipSuccess;
-    const size_t ldsBytes = static_cast<size_t>(a.rowStates) * kAlignPosteriorLdsBytesPerState;
-    hipLaunchKernelGGL(dev::alignPosteriorSweep, dim3(a.nSegments), dim3(kAlignThreads), ldsBytes, stream, a);
-    return launchItems(a, stream);
-}
-
-hipError_t launchAlignPosteriorsSearch(const AlignPosteriorSearchArgs& a, hipStream_t stream) {
-    if (a.call.nSegments == 0)
-        return hipSuccess;
-    const size_t ldsBytes = static_cast<size_t>(a.call.rowStates) * kAlignPosteriorLdsBytesPerState;
-    hipLaunchKernelGGL(dev::alignPosteriorSweepSearch, dim3(a.call.nSegments), dim3(kAlignThreads), ldsBytes, stream, a);
-    return launchItems(a.call, stream);
 }
 
 }  // namespace rasr_gmm

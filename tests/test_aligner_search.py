@@ -1,5 +1,5 @@
 """The search calls (gmm_aligner_align_search_*, gmm_aligner_posteriors_search_*; the retry loop and the n-best step of
-rasr_amd/csrc/gmm_align_search.hh) against the restatement of their contract (tests/aligner_search_restatement.py).
+rasr_amd/csrc/gmm_align_step.hh) against the restatement of their contract (tests/aligner_search_restatement.py).
 
 Viterbi mode: bit for bit -- scores, thresholds, iterations, hypotheses and the three column outputs.  Baum-Welch mode:
 thresholds, iterations, hypotheses, item membership, order and CSR exactly; out_score, out_log_total and the weights by
